@@ -18,6 +18,10 @@ Rosenbrock problems of dimension 32, L-BFGS m = 6, fp64, "parity stopping (B)"
 whole configs[2] batch (1,048,576 problems, sharded over the ranks: strong
 scaling, the G = 1, 2, 4, 8 rows of BASELINE.md section 4).
 
+A plain run does only what its headline figure needs: set-up, --warmup steps, --steps timed steps (`ms_per_step` = wall
+time of one), the line; `--dump-outputs DIR` also writes what the last timed step returned.  The counter passes, the CPU
+legs, the secondary figures and the strong configs[2] row described below run under `--full`.
+
 Rank 0 prints ONE JSON line — at EVERY N: under `--gpus N > 1` rank 0 still runs the counter passes (on its own device, its
 shard as a one-GPU child run), the CPU legs and the parity sample while the other ranks are parked on a host-side (gloo)
 group, after all collectives of the run.  Next to the contract's fields it carries
@@ -616,7 +620,17 @@ def parse_args(argv=None):
     ap.add_argument("--launch-plan", action="store_true",
                     help="print the launch decision (mode, command, rank plan, visible GPUs) as one JSON line and exit: "
                          "0 when the plan can run here, 3 when it cannot")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies beside the headline figure: the rocprofv3 counter passes, the CPU legs "
+                         "(cpu_baseline, cpu_reference, parity sample), the secondary figures and the strong configs[2] "
+                         "row; without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (x, f, g, the progress fields) as "
+                         "DIR/<name>.npy in float64 (at most 64 MB in all: a fixed, seeded sample of the problems above that)")
+    args = ap.parse_args(argv)
+    if not args.full:     # a plain run measures the headline only (--no-* then have nothing left to switch off)
+        args.no_cpu_baseline = args.no_secondary = args.no_counters = True
+    return args
 
 
 def main():
@@ -628,12 +642,47 @@ def main():
     if plan["error"]:
         raise SystemExit("bench.py: " + plan["error"])
     if plan["mode"] == "self-launch":
+        # the launcher runs as a child process, not in place of this one: counting the GPUs above may have initialised
+        # the GPU runtime here, and such a process must not replace its program
+        import signal
         sys.stdout.flush()
-        os.environ["MI355_BENCH_SELF_LAUNCHED"] = "1"
-        os.execv(sys.executable, plan["cmd"])
+        child = subprocess.Popen(plan["cmd"], env=dict(os.environ, MI355_BENCH_SELF_LAUNCHED="1"))
+        signal.signal(signal.SIGTERM, lambda signum, frame: child.send_signal(signum))
+        rc = child.wait()
+        raise SystemExit(rc if rc >= 0 else 128 - rc)
     line = run_bench(args, plan, GpuRuntime(plan))
     if line is not None:
         print(json.dumps(line))
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(directory, out, first_problem, rank=0, world=1):
+    """--dump-outputs: what one step returned to its caller — x, f, g and every field of the progress records — as float64
+    DIR/<name>.npy, with problem_index.npy naming the (global) problem of each row.  When the rows exceed this rank's share
+    of DUMP_BUDGET_BYTES, a fixed sample (seeded with SEED) of them is written; under N > 1 ranks every rank writes its shard
+    with the prefix rank<r>_."""
+    import torch
+    from cppnumericalsolvers_amd import capi
+    x, f, g, prog = out
+    B = int(x.shape[0])
+    fields = capi.PROGRESS_DTYPE.names
+    row_bytes = 8 * (x[0].numel() + (g[0].numel() if g is not None else 0) + 1 + len(fields) + 1)
+    rows = min(B, (DUMP_BUDGET_BYTES // world - 4096) // row_bytes)
+    idx = np.arange(B) if rows == B else np.sort(np.random.default_rng(SEED).choice(B, rows, replace=False))
+    it = torch.from_numpy(idx).to(x.device)
+    arrays = {"x": x[it], "f": f[it]}
+    if g is not None:
+        arrays["g"] = g[it]
+    arrays = {k: v.cpu().numpy().astype(np.float64) for k, v in arrays.items()}
+    records = prog.view(B, capi.PROGRESS_DTYPE.itemsize)[it].cpu().numpy().copy().view(capi.PROGRESS_DTYPE).reshape(-1)
+    arrays.update(("progress_" + k, records[k].astype(np.float64)) for k in fields)
+    arrays["problem_index"] = (first_problem + idx).astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    prefix = "rank%d_" % rank if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, prefix + name + ".npy"), a)
 
 
 def run_bench(args, plan, rt):
@@ -738,6 +787,8 @@ def run_bench(args, plan, rt):
         elapsed = float(t.item())
 
     x, f, g, prog = out
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, lo, rank, world)
     pn = amd.progress_to_numpy(prog)
     # ---- who actually solved: one record per rank (device identity, problems solved, kernel ms), gathered over RCCL ----
     mine = {"rank": rank, "device": rt.device_identity(), "solved": int(len(pn)), "kernel_ms": float(np.mean(kernel_ms))}

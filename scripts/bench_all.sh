@@ -15,8 +15,8 @@ for SPEC in $SPECS; do
   [[ "$NAME" == f_* ]] && WL=$(echo "$NAME" | cut -d_ -f1,2)
   EXTRA=""
   [[ "$SPEC" == *:* ]] && EXTRA=$(echo "${SPEC#*:}" | tr ':' ' ')
-  ARGS="--workload $WL $EXTRA --no-secondary"
-  [[ "$NAME" == "default" ]] && ARGS=""          # the driver's own command line: every secondary figure included
+  ARGS="--full --workload $WL $EXTRA --no-secondary"
+  [[ "$NAME" == "default" ]] && ARGS="--full"    # every secondary figure included
   timeout 900 python $ROOT/bench.py $ARGS > $OUT/${TAG}_bench_n1_$NAME.json 2> $OUT/${TAG}_bench_n1_$NAME.err
   python - <<PY
 import json

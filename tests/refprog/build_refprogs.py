@@ -10,10 +10,11 @@ binaries this leaves behind.  For every entry of programs.json:
      never travels);
   3. `<name>_ref`   = g++ of the program over /root/reference/include + oracle/eigen_shim  -> oracle/_ref/programs/
      `<name>_mi355` = g++ of the edited program over include/ + oracle/eigen_shim, linked against
-                      cppnumericalsolvers_amd/libmi355_lbfgs.so                          -> tests/cpp/_build/refprog/
+                      cppnumericalsolvers_amd/libmi355_lbfgs.so (found relative to the binary) -> oracle/_ref/programs/
      both with tests/refprog/prelude.h force-included (full-precision output; see there).
 
-Both directories are git-ignored and travel to the GPU box as binaries, like oracle/_ref/libref.so.  `--golden` also runs
+Both builds land in the git-ignored oracle/_ref/programs and travel with the tree as binaries, like oracle/_ref/libref.so;
+a `_mi355` binary loads the engine library that build() made next to it wherever the tree lies.  `--golden` also runs
 the `_ref` binaries (CPU only) and writes their outputs to tests/golden/reference_programs.json.
 """
 import argparse
@@ -28,7 +29,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 REFERENCE = "/root/reference"
 REF_OUT = os.path.join(ROOT, "oracle", "_ref", "programs")
-MI355_OUT = os.path.join(ROOT, "tests", "cpp", "_build", "refprog")
+MI355_OUT = REF_OUT
 GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_programs.json")
 SHIM = os.path.join(ROOT, "oracle", "eigen_shim")
 PRELUDE = os.path.join(HERE, "prelude.h")
@@ -106,7 +107,8 @@ def compile_program(program, build, tmp, force=False):
         cmd += ["-I", os.path.join(REFERENCE, "include")] + extra + [src, "-o", target]
     else:
         cmd += ["-Wall", "-Wextra", "-I", os.path.join(ROOT, "include")] + extra + [src, "-L", LIBDIR, "-l" + library, "-L/opt/rocm/lib",
-                "-lamdhip64", "-Wl,-rpath," + LIBDIR, "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-o", target]
+                "-lamdhip64", "-Wl,-rpath,$ORIGIN/" + os.path.relpath(LIBDIR, out_dir), "-Wl,-rpath,/opt/rocm/lib",
+                "-Wl,-rpath-link,/opt/rocm/lib", "-o", target]
     done = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if done.returncode != 0:
         # (compiler messages quote source lines: keep reference text out of logs that may be committed)

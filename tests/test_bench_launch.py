@@ -108,3 +108,49 @@ def test_cpu_legs_take_the_cores_of_the_box_under_a_launcher():
     assert bench.cpu_threads(1, {"LOCAL_RANK": "0", "TORCHELASTIC_RUN_ID": "x"}, affinity=128) == 128
     assert bench.cpu_threads(8, {}, affinity=128) == 8                    # no launcher: OpenMP's own default
     assert bench.cpu_threads(1, {"LOCAL_RANK": "0", "MI355_BENCH_CPU_THREADS": "5"}, affinity=128) == 5
+
+
+def test_a_plain_run_measures_the_headline_only_and_full_keeps_the_rest():
+    """Without --full no counter pass, CPU leg or secondary figure runs; --full brings them back, --no-* still apply."""
+    import bench
+    plain = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert (plain.steps, plain.warmup, plain.full, plain.dump_outputs) == (7, 2, False, None)
+    assert plain.no_counters and plain.no_cpu_baseline and plain.no_secondary
+    full = bench.parse_args(["--full"])
+    assert full.full and not (full.no_counters or full.no_cpu_baseline or full.no_secondary)
+    assert bench.parse_args(["--full", "--no-counters"]).no_counters
+
+
+def test_dump_outputs_writes_what_the_step_returned_as_float64_within_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    import bench
+    from cppnumericalsolvers_amd import capi
+    B, n = 1000, 8
+    rng = np.random.default_rng(1)
+    x, g, f = (torch.from_numpy(rng.normal(size=s)) for s in ((B, n), (B, n), (B,)))
+    rec = np.zeros(B, dtype=capi.PROGRESS_DTYPE)
+    rec["status"], rec["num_iterations"], rec["gradient_norm"] = 2, np.arange(B), 0.25
+    prog = torch.from_numpy(rec.view(np.uint8).copy())
+    bench.dump_outputs(str(tmp_path / "all"), (x, f, g, prog), first_problem=0)
+    names = {"x", "f", "g", "problem_index"} | {"progress_" + k for k in capi.PROGRESS_DTYPE.names}
+    assert {p.name for p in (tmp_path / "all").iterdir()} == {k + ".npy" for k in names}
+    got = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in names}
+    assert all(a.dtype == np.float64 for a in got.values())
+    np.testing.assert_array_equal(got["x"], x.numpy())
+    np.testing.assert_array_equal(got["g"], g.numpy())
+    np.testing.assert_array_equal(got["f"], f.numpy())
+    np.testing.assert_array_equal(got["progress_num_iterations"], np.arange(B))
+    assert np.all(got["progress_status"] == 2) and np.all(got["progress_gradient_norm"] == 0.25)
+    # above the budget: the same seeded sample of rows in every run, the files within the budget
+    row = 8 * (2 * n + 1 + len(capi.PROGRESS_DTYPE.names) + 1)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4096 + 300 * row)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), (x, f, g, prog), first_problem=5000)
+    idx = np.load(str(tmp_path / "a" / "problem_index.npy"))
+    np.testing.assert_array_equal(idx, np.load(str(tmp_path / "b" / "problem_index.npy")))
+    assert idx.size == 300 and np.all(np.diff(idx) > 0) and idx.min() >= 5000 and idx.max() < 5000 + B
+    rows = (idx - 5000).astype(np.int64)
+    np.testing.assert_array_equal(np.load(str(tmp_path / "a" / "x.npy")), x.numpy()[rows])
+    np.testing.assert_array_equal(np.load(str(tmp_path / "a" / "progress_num_iterations.npy")), rows)
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= bench.DUMP_BUDGET_BYTES

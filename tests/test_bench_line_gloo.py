@@ -108,7 +108,7 @@ def _worker(rank, world, port, out_path):
     env = {"RANK": str(rank), "LOCAL_RANK": str(rank), "WORLD_SIZE": str(world)}
     plan = bench.launch_plan(world, "auto", env, ["--gpus", str(world)], visible_gpus=world)
     assert plan["mode"] == "rank-of-launcher" and plan["error"] is None
-    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--batch", "512"]
+    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--batch", "512", "--full"]
     args = bench.parse_args()
     t0 = time.perf_counter()
     line = bench.run_bench(args, plan, _stand_in_runtime(bench, plan, port))

@@ -19,7 +19,7 @@ def _run(ranks, extra=()):
     env["MI355_BENCH_SHARED_DEVICE_DRY_RUN"] = str(ranks)
     env["MI355_BENCH_CPU_BUDGET_S"] = "1.0"
     t0 = time.perf_counter()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"] + list(extra),
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full"] + list(extra),
                        env=env, capture_output=True, text=True, timeout=600)
     return r, time.perf_counter() - t0
 
