@@ -70,6 +70,20 @@ class Stop(C.Structure):
     ]
 
 
+# ... and the trust-region solver's (checked by tests/test_trust_region_twin.py)
+TRUST_REGION_SYMBOLS = ["mi355_trust_region_default_config", "mi355_trust_region_newton_minimize_batch",
+                        "mi355_trust_region_newton_minimize_batch_host"]
+
+
+class TrustRegionConfig(C.Structure):
+    """mi355_trust_region_config = TrustRegionNewtonConfig<double> of the reference (same fields, same order)."""
+    _fields_ = [("initial_radius", C.c_double), ("max_radius", C.c_double), ("acceptance_threshold", C.c_double),
+                ("shrink_factor", C.c_double), ("expand_factor", C.c_double), ("rho_low", C.c_double),
+                ("rho_high", C.c_double), ("cg_forcing_coefficient", C.c_double),
+                ("cg_max_iterations_floor", C.c_int32), ("min_radius", C.c_double),
+                ("rejection_retry_limit", C.c_int32)]
+
+
 class Desc(C.Structure):
     """mi355_lbfgs_desc."""
     _fields_ = [
@@ -205,6 +219,11 @@ def _bind(L):
     L.mi355_lbfgs_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp]
     L.mi355_bfgs_minimize_batch.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mi355_bfgs_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp]
+    L.mi355_trust_region_default_config.argtypes = [C.POINTER(TrustRegionConfig)]
+    L.mi355_trust_region_newton_minimize_batch.argtypes = [vp, C.POINTER(Desc), C.POINTER(TrustRegionConfig), C.c_int64,
+                                                           vp, vp, vp, vp, vp, vp]
+    L.mi355_trust_region_newton_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), C.POINTER(TrustRegionConfig),
+                                                                C.c_int64, vp, vp, vp, vp, vp]
     L.mi355_lbfgsb_minimize_batch.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mi355_lbfgsb_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, vp, vp, vp, vp, vp]
     L.mi355_lbfgs_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -256,6 +275,17 @@ def check(rc):
             if msg:
                 break
         raise EngineError(rc, msg.decode() if msg else "")
+
+
+def default_trust_region_config(**overrides):
+    """mi355_trust_region_default_config(), with the named fields replaced."""
+    c = TrustRegionConfig()
+    check(load().mi355_trust_region_default_config(C.byref(c)))
+    for k, v in overrides.items():
+        if not hasattr(c, k):
+            raise TypeError("TrustRegionNewtonConfig has no field %r" % k)
+        setattr(c, k, v)
+    return c
 
 
 def default_stop(preset="default"):

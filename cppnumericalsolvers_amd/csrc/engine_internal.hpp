@@ -17,6 +17,7 @@
 #include "../../include/mi355_lbfgs.h"
 #include "lbfgs_kernel.hpp"
 #include "lbfgsb_kernel.hpp"
+#include "trust_region_config.hpp"
 
 constexpr int kQueueWords = 4;  // work-queue head (+ spare words), zeroed before every launch
 
@@ -193,6 +194,18 @@ using UserLbfgsbFn = int (*)(mi355_lbfgs_ctx* ctx, int W, int E, int linesearch,
 void register_user_lbfgsb(int objective_id, UserLbfgsbFn fn);
 struct UserLbfgsbRegistration {
   UserLbfgsbRegistration(int objective_id, UserLbfgsbFn fn) { register_user_lbfgsb(objective_id, fn); }
+};
+
+// TrustRegionNewton (dispatch_trust_region.hip, trust_region_kernel.hpp): W lanes per problem, one coordinate per lane
+int dispatch_trust_region(mi355_lbfgs_ctx* ctx, int W, int objective, const SolveArgs& args,
+                          const TrustRegionDeviceConfig& cfg, hipStream_t stream);
+// ... on a user functor with a hess_full: registered by the unit _build.py generates for trust_region=True
+using UserTrustRegionFn = int (*)(mi355_lbfgs_ctx* ctx, int W, const SolveArgs& args, const TrustRegionDeviceConfig& cfg,
+                                  hipStream_t stream);
+void register_user_trust_region(int objective_id, UserTrustRegionFn fn);
+UserTrustRegionFn user_trust_region(int objective_id);
+struct UserTrustRegionRegistration {
+  UserTrustRegionRegistration(int objective_id, UserTrustRegionFn fn) { register_user_trust_region(objective_id, fn); }
 };
 
 // desc->trace (device array pointers) -> the trace fields of SolveArgs; uploads the problem list, zeroes `written`

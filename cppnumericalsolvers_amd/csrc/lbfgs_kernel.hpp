@@ -860,6 +860,8 @@ __global__ __launch_bounds__((64 * solve_max_waves<W, E, OUTER, Obj>())) void lb
     x_delta = s_inf;                                     // :190
     gradient_norm = seg_amax<W, E>(g);                   // :195
     xinf_bound = (xinf_bound + x_delta) * (1.0 + 4.0 * eps);  // |x+_j| <= |x_j| + |x+_j - x_j|
+    // The tests of :212-317 below are also progress_device.hpp's progress_stop_tests (the trust-region kernel calls it);
+    // these kernels keep their inline copy for their register budgets.  A fix to one belongs in both.
     const mi355_lbfgs_stop& st = a.stop;
     status = MI355_STATUS_CONTINUE;
     bool decided = false;

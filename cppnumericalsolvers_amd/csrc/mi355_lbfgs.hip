@@ -28,6 +28,7 @@ namespace {
 struct UserEntry {
   UserDispatchFn fn[4] = {nullptr, nullptr, nullptr, nullptr};  // lanes per problem 8, 16, 32, 64
   UserLbfgsbFn lbfgsb = nullptr;
+  UserTrustRegionFn trust_region = nullptr;
   std::string name;
 };
 std::vector<std::pair<int, UserEntry>>& user_table() {
@@ -60,6 +61,23 @@ void register_user_lbfgsb(int objective_id, UserLbfgsbFn fn) {
   UserEntry u;
   u.lbfgsb = fn;
   user_table().emplace_back(objective_id, u);
+}
+void register_user_trust_region(int objective_id, UserTrustRegionFn fn) {
+  if (objective_id < MI355_OBJ_USER_FIRST) return;
+  for (auto& e : user_table()) {
+    if (e.first == objective_id) {
+      e.second.trust_region = fn;
+      return;
+    }
+  }
+  UserEntry u;
+  u.trust_region = fn;
+  user_table().emplace_back(objective_id, u);
+}
+UserTrustRegionFn user_trust_region(int objective_id) {
+  for (auto& e : user_table())
+    if (e.first == objective_id) return e.second.trust_region;
+  return nullptr;
 }
 static const UserEntry* find_user_objective(int objective_id) {
   for (auto& e : user_table())
@@ -1182,3 +1200,99 @@ int mi355_lbfgs_selftest(mi355_lbfgs_ctx* ctx, int32_t* lane_maps, const double*
 }
 
 }  // extern "C"
+
+// ---- TrustRegionNewton (trust_region_kernel.hpp) -------------------------------------------------------------------
+extern "C" int mi355_trust_region_default_config(mi355_trust_region_config* out) {
+  if (!out) return fail(MI355_ERR_INVALID_ARGUMENT, "null config");
+  out->initial_radius = 1.0;        // trust_region_newton.h TrustRegionNewtonConfig defaults
+  out->max_radius = 1e10;
+  out->acceptance_threshold = 0.15;
+  out->shrink_factor = 0.25;
+  out->expand_factor = 2.0;
+  out->rho_low = 0.25;
+  out->rho_high = 0.75;
+  out->cg_forcing_coefficient = 0.5;
+  out->cg_max_iterations_floor = 10;
+  out->min_radius = 1e-12;
+  out->rejection_retry_limit = 50;
+  return MI355_OK;
+}
+
+extern "C" int mi355_trust_region_newton_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc_in,
+                                                        const mi355_trust_region_config* config, int64_t B,
+                                                        const double* x0, double* x_out, double* f_out, double* g_out,
+                                                        mi355_lbfgs_progress* progress_out, void* stream_) {
+  if (!desc_in) return fail(MI355_ERR_INVALID_ARGUMENT, "null desc");
+  // m and the line search mean nothing to this solver; the Hessian always comes from the functor
+  mi355_lbfgs_desc desc = *desc_in;
+  desc.m = 1;
+  desc.linesearch = MI355_LS_MORE_THUENTE;
+  desc.history_placement = 0;
+  if (desc.hessian_diagonal != nullptr)
+    return fail(MI355_ERR_INVALID_ARGUMENT, "TrustRegionNewton: H(x) comes from the device functor (hessian_diagonal NULL)");
+  desc.hessian_from_functor = 1;
+  if (desc.n > kHessianConditionMaxN)
+    return fail(MI355_ERR_UNSUPPORTED, "TrustRegionNewton is built for n <= 64 (H is n x n in LDS per problem)");
+  int rc = validate(ctx, &desc, B);
+  if (rc != MI355_OK) return rc;
+  if (desc.arithmetic == MI355_ARITH_FMA)
+    return fail(MI355_ERR_UNSUPPORTED, "TrustRegionNewton is built for the exact arithmetic only (no MI355_ARITH_FMA)");
+  if (desc.objective != MI355_OBJ_ROSENBROCK && desc.objective != MI355_OBJ_DIAG_QUADRATIC &&
+      !(desc.objective >= MI355_OBJ_USER_FIRST && user_trust_region(desc.objective) != nullptr))
+    return fail(MI355_ERR_UNSUPPORTED,
+                desc.objective >= MI355_OBJ_USER_FIRST
+                    ? "TrustRegionNewton: this library holds no trust-region kernel for this user objective (build it with "
+                      "trust_region=True and a functor that defines hess_full)"
+                    : "TrustRegionNewton is built for objectives with a device Hessian (hess_full): Rosenbrock, "
+                      "DiagQuadratic and user functors; the ridge forms, the augmented-Lagrangian composite and sum / "
+                      "product records have none");
+  if (desc.elems_per_lane != 0 && desc.elems_per_lane != 1)
+    return fail(MI355_ERR_INVALID_ARGUMENT, "TrustRegionNewton: one coordinate per lane (elems_per_lane 0 or 1)");
+  int W = desc.lanes_per_problem;
+  if (W == 0) {
+    W = 8;
+    while (W < desc.n) W <<= 1;
+  } else if (!(W == 8 || W == 16 || W == 32 || W == 64) || W < desc.n) {
+    return fail(MI355_ERR_INVALID_ARGUMENT, "TrustRegionNewton: lanes_per_problem must be 8, 16, 32 or 64 and cover n");
+  }
+  mi355_trust_region_config c;
+  mi355_trust_region_default_config(&c);
+  if (config) c = *config;
+  TrustRegionDeviceConfig dc;
+  dc.initial_radius = c.initial_radius;
+  dc.max_radius = c.max_radius;
+  dc.acceptance_threshold = c.acceptance_threshold;
+  dc.shrink_factor = c.shrink_factor;
+  dc.expand_factor = c.expand_factor;
+  dc.rho_low = c.rho_low;
+  dc.rho_high = c.rho_high;
+  dc.cg_forcing_coefficient = c.cg_forcing_coefficient;
+  dc.min_radius = c.min_radius;
+  dc.cg_extra_iterations = c.cg_max_iterations_floor > 0 ? c.cg_max_iterations_floor : 0;
+  dc.rejection_retry_limit = c.rejection_retry_limit < 0 ? 0 : (c.rejection_retry_limit > 1000 ? 1000 : c.rejection_retry_limit);
+  if (B == 0) return MI355_OK;
+  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MI355_ENTER_DEVICE(ctx);
+  rc = upload_params(ctx, &desc, W, 1, stream);
+  if (rc != MI355_OK) return rc;
+  SolveArgs args;
+  std::memset(&args, 0, sizeof(args));
+  args.x0 = x0;
+  args.x_out = x_out;
+  args.f_out = f_out;
+  args.g_out = g_out;
+  args.progress_out = progress_out;
+  args.obj_params = ctx->params_dev;
+  args.per_problem = desc.per_problem_data;
+  args.per_problem_stride = desc.per_problem_stride;
+  args.B = B;
+  args.n = desc.n;
+  args.m = 1;
+  args.stop = desc.stop;
+  args.hess_from_functor = 1;
+  args.hessian_condition_stop = desc.hessian_condition_stop;
+  rc = setup_trace(ctx, &desc, B, stream, args);
+  if (rc != MI355_OK) return rc;
+  return dispatch_trust_region(ctx, W, desc.objective, args, dc, stream);
+}

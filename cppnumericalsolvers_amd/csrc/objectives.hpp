@@ -234,6 +234,26 @@ struct DiagQuadraticObjective {
   }
 };
 
+// DiagQuadratic with its Hessian in full, for the trust-region kernel (trust_region_kernel.hpp): H = diag(2 a_i), column
+// major n x n in the segment's LDS.  A type of its own, as RosenbrockConditionObjective: the Lbfgs kernels read
+// HasHessFull to decide whether they carry the condition_hessian LU.  Negative a_i give the indefinite model.
+template <int E>
+struct DiagQuadraticHessObjective : DiagQuadraticObjective<E> {
+  template <int W, int EE>
+  __device__ __forceinline__ void hess_full(const double (&)[EE], double* Hm, int n, int sl) const {
+    for (int t = sl; t < n * n; t += W) Hm[t] = 0.0;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int e = 0; e < EE; ++e) {
+      const int j = sl * EE + e;
+      if (j < n) Hm[j * n + j] = 2.0 * this->coefficient(e, sl);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+};
+
 // Ridge least squares  f(x) = ||A x - y_b||^2 + lambda ||x||^2: the reference README's
 // `SquaredError(A, y) + lambda * L2Reg(n)` (README.md:122-167) through the First-mode
 // branches of AddExpression / MulExpression (function_expressions.h:115-124, :229-236):

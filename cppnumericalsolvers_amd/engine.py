@@ -423,6 +423,65 @@ class BatchedBfgs(BatchedLbfgs):
                          elems_per_lane=elems_per_lane)
 
 
+class BatchedTrustRegionNewton(BatchedLbfgs):
+    """Batched `TrustRegionNewton<F>` (reference solver/trust_region_newton.h): one Hessian per outer step, CG-Steihaug
+    on the quadratic model, the agreement ratio, the radius update and the in-step rejection loop; n <= 64, objectives
+    whose device functor has a hess_full (Rosenbrock, DiagQuadratic, user functors built with trust_region=True).
+
+    The keyword arguments are the fields of TrustRegionNewtonConfig (same names and defaults); `condition_hessian` is
+    stopping_progress.condition_hessian (0 = off).  progress.sum_k holds the solve's total CG iterations."""
+    _entry = "mi355_trust_region_newton_minimize_batch"
+
+    def __init__(self, stopping_progress=None, device=0, context=None, lanes_per_problem=0, condition_hessian=0.0,
+                 **config):
+        super().__init__(m=1, stopping_progress=stopping_progress, device=device, context=context,
+                         arithmetic="exact", lanes_per_problem=lanes_per_problem, condition_hessian=condition_hessian)
+        self.config = capi.default_trust_region_config(**config)
+
+    def _desc(self, objective, n, per_problem=None, per_problem_stride=0):
+        d = super()._desc(objective, n, per_problem, per_problem_stride)
+        d.hessian_from_functor = 0     # (H(x) always comes from the device functor's hess_full)
+        d.hessian_diagonal = None
+        d.hessian_condition = 0.0
+        d.hessian_condition_stop = self.condition_hessian
+        return d
+
+    def minimize(self, objective, x0, want_gradient=True, want_progress=True, per_problem=None, trace=None):
+        torch = self._torch
+        if x0.dtype != torch.float64 or x0.dim() != 2 or not x0.is_cuda:
+            raise ValueError("x0 must be a [B, n] float64 CUDA tensor")
+        self._on_device(x0, "x0")
+        x0 = x0.contiguous()
+        B, n = x0.shape
+        x = torch.empty_like(x0)
+        f = torch.empty(B, dtype=torch.float64, device=x0.device)
+        g = torch.empty_like(x0) if want_gradient else None
+        prog = torch.empty(B * capi.PROGRESS_DTYPE.itemsize, dtype=torch.uint8, device=x0.device) \
+            if want_progress else None
+        d = self._desc(objective, n, *self._pp_device(per_problem, B))
+        if trace is not None:
+            self._trace_keepalive = trace
+            d.trace = trace.c_pointer()
+        capi.check(self.ctx._lib.mi355_trust_region_newton_minimize_batch(
+            self.ctx.handle, C.byref(d), C.byref(self.config), B, x0.data_ptr(), x.data_ptr(), f.data_ptr(),
+            g.data_ptr() if g is not None else None, prog.data_ptr() if prog is not None else None, self._stream()))
+        return x, f, g, prog
+
+    def minimize_host(self, objective, x0, per_problem=None):
+        """Same through the host-pointer entry point (numpy in, numpy out, synchronous)."""
+        if per_problem is not None:
+            raise ValueError("per-problem data: use minimize() with device tensors")
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        B, n = x0.shape
+        x, g, f = np.empty_like(x0), np.empty_like(x0), np.empty(B)
+        prog = np.zeros(B, dtype=capi.PROGRESS_DTYPE)
+        d = self._desc(objective, n)
+        capi.check(self.ctx._lib.mi355_trust_region_newton_minimize_batch_host(
+            self.ctx.handle, C.byref(d), C.byref(self.config), B, x0.ctypes.data, x.ctypes.data, f.ctypes.data,
+            g.ctypes.data, prog.ctypes.data))
+        return x, f, g, prog
+
+
 class BatchedLbfgsb(BatchedLbfgs):
     """Batched `Lbfgsb<F, m>` (reference solver/lbfgsb.h, default m = 5; built for m <= 10): box-constrained L-BFGS-B.
 

@@ -364,6 +364,53 @@ int mi355_bfgs_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc*
                                    double* x_out, double* f_out, double* g_out,
                                    mi355_lbfgs_progress* progress_out);
 
+/* ---- TrustRegionNewton ----------------------------------------------------
+ * cppoptlib::solver::TrustRegionNewtonConfig<double> (solver/trust_region_newton.h): the same fields, names, order and
+ * defaults.  mi355_trust_region_default_config() fills the defaults. */
+typedef struct mi355_trust_region_config {
+  double initial_radius;          /* 1 */
+  double max_radius;              /* 1e10 */
+  double acceptance_threshold;    /* 0.15: a step is accepted when rho > this */
+  double shrink_factor;           /* 0.25 */
+  double expand_factor;           /* 2 */
+  double rho_low;                 /* 0.25: the radius shrinks when rho < this */
+  double rho_high;                /* 0.75: ... grows when rho > this and the step hit the boundary */
+  double cg_forcing_coefficient;  /* 0.5 */
+  int32_t cg_max_iterations_floor; /* 10: CG-Steihaug runs at most max(this, 0) iterations: the reference adds its
+                                      dim_, which InitializeSolver leaves at 0 */
+  double min_radius;              /* 1e-12 */
+  int32_t rejection_retry_limit;  /* 50 (clamped to [0, 1000] as the reference does) */
+} mi355_trust_region_config;
+int mi355_trust_region_default_config(mi355_trust_region_config* out);
+
+/* Trust-region Newton: replaces cppoptlib::solver::TrustRegionNewton<FunctionType>::Minimize (trust_region_newton.h under
+ * Solver::Minimize, solver/solver.h:181-224) for B problems at once, one problem per segment of a wavefront, H(x) n x n in
+ * LDS (built from the device functor's hess_full once per accepted iterate), CG-Steihaug on the model, the agreement
+ * ratio, the radius update and the in-step rejection loop of the reference; the stopping tests of Progress::Update
+ * (desc->stop), including condition_hessian (desc->hessian_condition_stop > 0: ||H(x)|| ||H(x)^-1|| on the device).
+ * Objectives whose device functor has a hess_full: Rosenbrock, DiagQuadratic, and user functors built with
+ * trust_region=True; n <= 64; exact arithmetic only (MI355_ARITH_FMA is refused).  Everything else returns
+ * MI355_ERR_UNSUPPORTED with the reason.  desc->m, linesearch, history_placement and hessian_from_functor are ignored;
+ * hessian_diagonal must be NULL.  Mapping: lanes_per_problem 0 = the library's choice (the padded width of n, at least
+ * 8) or 8, 16, 32, 64 >= n; elems_per_lane 0 or 1.  Results do not depend on the mapping.  config NULL = the defaults.
+ * The fields of mi355_lbfgs_progress for this solver:
+ *   num_iterations  outer steps (Progress::num_iterations)
+ *   nfev            the objective calls the reference makes, the Hessian-only call of Progress::Update not counted:
+ *                   1 at the start, then per step 1 for g and H, 1 per trial point and 1 more on acceptance (a rejection
+ *                   loop that retries an identical subproblem is counted in full)
+ *   sum_k           the total number of CG-Steihaug iterations of the solve
+ *   x_delta, f_delta, gradient_norm: as for the other solvers (a stalled step gives x_delta = 0). */
+int mi355_trust_region_newton_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
+                                             const mi355_trust_region_config* config, int64_t B, const double* x0,
+                                             double* x_out, double* f_out, double* g_out,
+                                             mi355_lbfgs_progress* progress_out, void* stream);
+/* The same with host arrays (g_out and progress_out may be NULL): pinned staging and chunks, as the other _host entry
+ * points; returns when the results are in the host arrays. */
+int mi355_trust_region_newton_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
+                                                  const mi355_trust_region_config* config, int64_t B, const double* x0,
+                                                  double* x_out, double* f_out, double* g_out,
+                                                  mi355_lbfgs_progress* progress_out);
+
 /* Duration in ms of the most recent solve kernel on this context, measured with
  * HIP events recorded on the launch stream; blocks until that kernel finished. */
 int mi355_lbfgs_last_kernel_ms(mi355_lbfgs_ctx* ctx, float* ms);
