@@ -38,6 +38,7 @@ int launch_ridge_mfma_mapping(mi355_lbfgs_ctx* ctx, SolveArgs args, hipStream_t 
   ctx->last_threads = kWaves * kWave;
   ctx->last_lds = lds;
   ctx->last_mr = MR;
+  ctx->last_variant = MI355_KERNEL_GENERAL;
   ctx->last_arith = AR::kFma ? MI355_ARITH_FMA : MI355_ARITH_EXACT;
   return MI355_OK;
 }

@@ -70,11 +70,13 @@ struct mi355_lbfgs_ctx {
   bool ev_start_armed = false;  // the caller recorded ev_start before its own preparatory kernels: launch_solve keeps it
   bool timed = false;
   int last_W = 0, last_E = 0, last_blocks = 0, last_threads = 0, last_lds = 0, last_mr = 0, last_arith = 0;
+  int last_variant = 0;  // MI355_KERNEL_GENERAL / MI355_KERNEL_LEAN: what launch_solve ran (mi355_lbfgs_last_kernel_variant)
   // experiment knobs, read ONCE from the environment when the context is created (mi355_lbfgs_create prints a notice
   // when one is set; 0 = not set): MI355_DEBUG_SOLVE_WAVES caps the wavefronts of a workgroup, MI355_DEBUG_SOLVE_BLOCKS
   // the resident grid; neither changes a result (scripts/ and profiles/ say where they were used)
   int debug_waves = 0;
   long long debug_blocks = 0;
+  int debug_general_kernel = 0;  // MI355_DEBUG_GENERAL_KERNEL: never pick the lean solve kernels (A/B runs on one library)
 };
 
 namespace mi355 {
@@ -156,6 +158,10 @@ int dispatch_lbfgsb_e(mi355_lbfgs_ctx* ctx, int E, int objective, int linesearch
 // More-Thuente, Rosenbrock / DiagQuadratic, m <= 8 (n <= 64) or m <= 5 (n <= 128); 32 lanes for m = 9, 10 (n <= 64)
 int dispatch_lbfgsb_fast(mi355_lbfgs_ctx* ctx, int W, int E, int objective, const LbfgsbArgs& args, hipStream_t stream);
 int dispatch_lbfgsb_fast_w32(mi355_lbfgs_ctx* ctx, int E, int objective, const LbfgsbArgs& args, hipStream_t stream);
+// The lean solve kernels (dispatch_lean.hip): lbfgs_solve_kernel<W, 4, RosenbrockFullObjective, 6 | 10, ..., ArithFma,
+// LeanOptions> for W = 8, 16 — the shapes of the flagship batches — with the options of a plain First-mode solve fixed at
+// compile time (lbfgs_kernel.hpp, LeanOptions).  launch_solve_rosenbrock_full picks them when lean_options_hold(args).
+int dispatch_lean(mi355_lbfgs_ctx* ctx, int W, int mr, const SolveArgs& args, hipStream_t stream);
 // ridge objective on the matrix cores (ridge_mfma_kernel.hpp): workgroups of sixteen problem slots
 int launch_ridge_mfma(mi355_lbfgs_ctx* ctx, SolveArgs args, hipStream_t stream, int lanes, bool fma);
 
@@ -235,7 +241,7 @@ inline hipError_t wait_for_last_solve(mi355_lbfgs_ctx* ctx, hipStream_t previous
 #ifdef MI355_DISPATCH_TU  // the launch templates are only needed where kernels are instantiated
 
 template <int W, int E, class Obj, int MR, int LS = MI355_LS_MORE_THUENTE, int ALG = kAlgLbfgs, class OUTER = NoOuterLoop,
-          class AR = ArithExact>
+          class AR = ArithExact, class OPT = RunTimeOptions>
 int launch_solve(mi355_lbfgs_ctx* ctx, SolveArgs args, hipStream_t stream, const typename OUTER::Args& outer_args = {}) {
   constexpr int kSegs = kWave / W;
   constexpr int kLdsLimit = 160 * 1024;
@@ -274,7 +280,11 @@ int launch_solve(mi355_lbfgs_ctx* ctx, SolveArgs args, hipStream_t stream, const
   const int lds = lds_shared + waves * lds_wave;
   const long long segs_per_block = static_cast<long long>(kSegs) * waves;
   const long long blocks_needed = (args.B + segs_per_block - 1) / segs_per_block;
-  auto kern = lbfgs_solve_kernel<W, E, Obj, MR, LS, ALG, OUTER, AR>;
+  if constexpr (OPT::kFixed) {
+    if (!lean_options_hold<OPT>(args))
+      return fail(MI355_ERR_INVALID_ARGUMENT, "internal: a solve kernel with fixed options was picked for a call they do not hold for");
+  }
+  auto kern = lbfgs_solve_kernel<W, E, Obj, MR, LS, ALG, OUTER, AR, OPT>;
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                               hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   // Persistent grid: as many workgroups as the chip holds at once (bounded by LDS and
@@ -290,7 +300,7 @@ int launch_solve(mi355_lbfgs_ctx* ctx, SolveArgs args, hipStream_t stream, const
 #ifdef MI355_LBFGS_PHASE_TIMING
   HIP_TRY(profile_counters(ctx, stream, &args.profile));
 #endif
-  if constexpr (kRegScalars || kBfgs) {
+  if constexpr ((kRegScalars || kBfgs) && !OPT::kFixed) {
     // plateau rings: MAX_PAST doubles per resident segment
     const size_t need = static_cast<size_t>(blocks_ll) * waves * kSegs * MI355_LBFGS_MAX_PAST;
     if (need > ctx->scratch_cap)  // (sized in mi355_lbfgs_create for the fullest resident grid)
@@ -310,6 +320,7 @@ int launch_solve(mi355_lbfgs_ctx* ctx, SolveArgs args, hipStream_t stream, const
   ctx->last_lds = lds;
   ctx->last_mr = MR;
   ctx->last_arith = AR::kFma ? MI355_ARITH_FMA : MI355_ARITH_EXACT;
+  ctx->last_variant = OPT::kFixed ? MI355_KERNEL_LEAN : MI355_KERNEL_GENERAL;
   return MI355_OK;
 }
 
@@ -406,6 +417,9 @@ int launch_solve_rosenbrock_full(mi355_lbfgs_ctx* ctx, int mr, const SolveArgs& 
   constexpr int MT = MI355_LS_MORE_THUENTE;
   const bool fma = (mr & kArithFmaBit) != 0;
   mr &= ~kArithFmaBit;
+  if constexpr (E == 4 && (W == 8 || W == 16)) {
+    if (fma && !ctx->debug_general_kernel && lean_options_hold<LeanOptions>(args)) return dispatch_lean(ctx, W, mr, args, stream);
+  }
   if (fma)
     return mr == 6 ? launch_solve<W, E, Obj, 6, MT, kAlgLbfgs, NO, ArithFma>(ctx, args, stream)
                    : launch_solve<W, E, Obj, 10, MT, kAlgLbfgs, NO, ArithFma>(ctx, args, stream);
@@ -603,6 +617,7 @@ int launch_lbfgsb(mi355_lbfgs_ctx* ctx, LbfgsbArgs args, hipStream_t stream, con
   ctx->last_threads = kWave;
   ctx->last_lds = lds;
   ctx->last_mr = 0;
+  ctx->last_variant = MI355_KERNEL_GENERAL;
   ctx->last_arith = MI355_ARITH_EXACT;
   return MI355_OK;
 }

@@ -262,9 +262,36 @@ __host__ __device__ constexpr int solve_max_waves() {
   return (E >= 8) ? 1 : (((OUTER::kEnabled || LargeFootprint<Obj>::value) && W == 64 && E == 4) ? 4 : 8);
 }
 
+// OPT: launch-options policy.  RunTimeOptions (the default): every option of the call — trace, preconditioner, problem map,
+// device-side count, which stopping tests are enabled — is a kernel argument tested where it matters, every pass.
+// FixedOptions<...>: the options of a plain First-mode solve are compile-time facts (lean_options_hold() below is the
+// host's side of the contract): no trace, no preconditioner, no Hessian-condition test, no problem map or device-side
+// count, no plateau ring (stop.past == 0); whether the f_delta test is enabled and whether the gradient test is relative
+// are the two template arguments.  The THRESHOLDS (x_delta, gradient_norm, num_iterations, x_delta_violations) stay
+// kernel arguments.  Only scalar and control work differs: every fp64 operation of the general kernel is there, in the
+// same order, so both return the same bits (tests/test_gpu_lean_kernel.py).
+struct RunTimeOptions {
+  static constexpr bool kFixed = false;
+  static constexpr bool kFDeltaTest = true, kGradientNormRelative = true;  // (not read)
+};
+template <bool F_DELTA_TEST, bool GRADIENT_NORM_RELATIVE>
+struct FixedOptions {
+  static constexpr bool kFixed = true;
+  static constexpr bool kFDeltaTest = F_DELTA_TEST, kGradientNormRelative = GRADIENT_NORM_RELATIVE;
+};
+// parity_stop(), its variant A (x_delta = 1e-9) and every other stop record with f_delta = 0, a relative gradient test and
+// past = 0.  (The reference's default preset has past = 3 and takes the general kernel.)
+using LeanOptions = FixedOptions<false, true>;
+template <class OPT>
+inline bool lean_options_hold(const SolveArgs& a) {
+  return a.trace == nullptr && a.precond == nullptr && a.hess_from_functor == 0 && a.hessian_condition_fires == 0 &&
+         !(a.hessian_condition_stop > 0.0) && a.count_dev == nullptr && a.problem_map == nullptr && a.stop.past == 0 &&
+         (a.stop.f_delta > 0) == OPT::kFDeltaTest && (a.stop.gradient_norm_relative != 0) == OPT::kGradientNormRelative;
+}
+
 // AR: arithmetic policy (wave_primitives.hpp): ArithExact, or ArithFma (Lbfgs with either line search; round 6: Hager-Zhang too).
 template <int W, int E, class Obj, int MR, int LS = MI355_LS_MORE_THUENTE, int ALG = 0, class OUTER = NoOuterLoop,
-          class AR = ArithExact>
+          class AR = ArithExact, class OPT = RunTimeOptions>
 // (Forcing 3 waves/SIMD on the E = 4, MR = 6 variant via launch bounds costs 48 B/lane of scratch
 // and 15 % of throughput — measured — so the allocator is left alone.)
 __global__ __launch_bounds__((64 * solve_max_waves<W, E, OUTER, Obj>())) void lbfgs_solve_kernel(const SolveArgs a, const typename OUTER::Args oa) {
@@ -282,7 +309,7 @@ __global__ __launch_bounds__((64 * solve_max_waves<W, E, OUTER, Obj>())) void lb
 
   const int n = a.n;
   const int m = a.m;
-  const long long queue_length = a.count_dev ? static_cast<long long>(*a.count_dev) : a.B;
+  const long long queue_length = (!OPT::kFixed && a.count_dev) ? static_cast<long long>(*a.count_dev) : a.B;
   // the two stopping fields an outer loop changes between the solves of one problem (uniform otherwise)
   [[maybe_unused]] unsigned long long stop_num_iterations = a.stop.num_iterations;
   [[maybe_unused]] double stop_gradient_norm = a.stop.gradient_norm;
@@ -290,6 +317,8 @@ __global__ __launch_bounds__((64 * solve_max_waves<W, E, OUTER, Obj>())) void lb
   constexpr bool kBfgs = (ALG == kAlgBfgs);
   static_assert(!kBfgs || MR == 0, "dense BFGS keeps no (s, y) history");
   static_assert(!AR::kFma || !kBfgs, "the fused arithmetic is built for Lbfgs (either line search), not for dense BFGS");
+  static_assert(!OPT::kFixed || (MR > 0 && !kBfgs && !OUTER::kEnabled),
+                "fixed launch options: plain Lbfgs solves with the y history in registers");
   constexpr bool kRegScalars = scalars_in_registers(E, MR, Obj::kLdsDoubles);
   constexpr bool kGlobalPast = kRegScalars || kBfgs;  // plateau ring in global scratch
   const int lds_problem = kBfgs ? bfgs_lds_doubles_per_problem(WE, Obj::kLdsDoubles)
@@ -305,6 +334,7 @@ __global__ __launch_bounds__((64 * solve_max_waves<W, E, OUTER, Obj>())) void lb
   double* const alpha_mem = rho_mem + m;
   // plateau ring (progress.h:139-140): LDS, or one MAX_PAST slot per resident segment in global scratch
   double* const past_f =
+      OPT::kFixed ? nullptr :
       kGlobalPast ? a.scratch + ((static_cast<size_t>(blockIdx.x) * (blockDim.x / kWave) + wave_in_block) * kSegs + seg) *
                                  MI355_LBFGS_MAX_PAST
                   : alpha_mem + m;
@@ -433,7 +463,7 @@ __global__ __launch_bounds__((64 * solve_max_waves<W, E, OUTER, Obj>())) void lb
         MI355_LPHASE(9);  // start point from HBM
         if (prob >= queue_length) break;  // queue drained: this segment is done
         const KernargSolveArgs ca = cold_args();
-        {
+        if constexpr (!OPT::kFixed) {
           const int* const map = ca->problem_map;
           if (map != nullptr) prob = map[prob];
         }
@@ -617,8 +647,8 @@ __global__ __launch_bounds__((64 * solve_max_waves<W, E, OUTER, Obj>())) void lb
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         const int j = sl * E + e;
-        d[e] = (a.precond != nullptr) ? ((j < n) ? a.precond[j] : 0.0) * d[e]   // :177-179
-                                      : d[e] * scaling_factor;                  // :181
+        d[e] = (!OPT::kFixed && a.precond != nullptr) ? ((j < n) ? a.precond[j] : 0.0) * d[e]   // :177-179
+                                                      : d[e] * scaling_factor;                  // :181
       }
       if constexpr (!kRegScalars) segment_lds_fence();
       // second loop, oldest -> newest (:185-196).  With a full history (the steady state) the first
@@ -880,6 +910,7 @@ __global__ __launch_bounds__((64 * solve_max_waves<W, E, OUTER, Obj>())) void lb
         x_delta_violations = 0;
       }
     }
+    if constexpr (!OPT::kFixed || OPT::kFDeltaTest)
     if (!decided) {                                      // :263-277
       const double fscale =
           st.f_delta_relative ? dmax(dmax(__builtin_fabs(f), __builtin_fabs(fprev)), 1.0) : 1.0;
@@ -893,6 +924,7 @@ __global__ __launch_bounds__((64 * solve_max_waves<W, E, OUTER, Obj>())) void lb
         f_delta_violations = 0;
       }
     }
+    if constexpr (!OPT::kFixed)
     if (!decided && st.past > 0) {                       // :280-298
       const int p = st.past;
       if (!past_init) {
@@ -916,7 +948,7 @@ __global__ __launch_bounds__((64 * solve_max_waves<W, E, OUTER, Obj>())) void lb
       }
     }
     if (!decided && stop_gradient_norm > 0) {            // :299-317
-      if (st.gradient_norm_relative) {
+      if (OPT::kFixed ? OPT::kGradientNormRelative : st.gradient_norm_relative) {
         // scale = max(1, ||x||_inf) <= max(1, bound): if even the bound's threshold is not
         // reached the test cannot fire and ||x||_inf need not be computed.
         if (gradient_norm < stop_gradient_norm * dmax(1.0, xinf_bound)) {
@@ -928,7 +960,7 @@ __global__ __launch_bounds__((64 * solve_max_waves<W, E, OUTER, Obj>())) void lb
         status = MI355_STATUS_GRADIENT_NORM_VIOLATION;
       }
     }
-    if (status == MI355_STATUS_CONTINUE && a.hessian_condition_fires)   // :318-325 (Second mode)
+    if (!OPT::kFixed && status == MI355_STATUS_CONTINUE && a.hessian_condition_fires)   // :318-325 (Second mode)
       status = MI355_STATUS_HESSIAN_CONDITION_VIOLATION;
     if constexpr (HasHessFull<Obj>::value && MR == 0 && !kBfgs && !OUTER::kEnabled) {
       // the same test for a Hessian that is not constant: H(x) of the new iterate, every iteration (:203-210)
@@ -942,7 +974,7 @@ __global__ __launch_bounds__((64 * solve_max_waves<W, E, OUTER, Obj>())) void lb
       }
     }
     MI355_LPHASE(6);  // results / refill
-    if constexpr (!OUTER::kEnabled)
+    if constexpr (!OUTER::kEnabled && !OPT::kFixed)
       trace_iteration<E>(a, prob, n, sl, num_iterations, status, f, x_delta, f_delta, gradient_norm, x, g);
     if constexpr (OUTER::kEnabled) {
       if (status != MI355_STATUS_CONTINUE) {

@@ -62,6 +62,7 @@ int launch_wide(mi355_lbfgs_ctx* ctx, WideArgs args, hipStream_t stream) {
   ctx->last_threads = T;
   ctx->last_lds = lds;
   ctx->last_mr = 0;
+  ctx->last_variant = MI355_KERNEL_GENERAL;
   ctx->last_arith = MI355_ARITH_EXACT;
   return MI355_OK;
 }

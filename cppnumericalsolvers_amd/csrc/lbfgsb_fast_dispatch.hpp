@@ -38,6 +38,7 @@ int launch_lbfgsb_fast(mi355_lbfgs_ctx* ctx, LbfgsbArgs args, hipStream_t stream
   ctx->last_threads = kWave;
   ctx->last_lds = lds;
   ctx->last_mr = 0;
+  ctx->last_variant = MI355_KERNEL_GENERAL;
   ctx->last_arith = MI355_ARITH_FMA;
   return MI355_OK;
 }

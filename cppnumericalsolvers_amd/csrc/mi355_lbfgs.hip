@@ -472,6 +472,10 @@ int mi355_lbfgs_create(int device, mi355_lbfgs_ctx** out) {
     std::fprintf(stderr, "mi355_lbfgs: EXPERIMENT knobs active on this context (MI355_DEBUG_SOLVE_WAVES=%d, "
                          "MI355_DEBUG_SOLVE_BLOCKS=%lld): the resident grid is capped; results are unchanged\n",
                  ctx->debug_waves, ctx->debug_blocks);
+  if (const char* dbg = std::getenv("MI355_DEBUG_GENERAL_KERNEL")) ctx->debug_general_kernel = std::atoi(dbg);
+  if (ctx->debug_general_kernel)
+    std::fprintf(stderr, "mi355_lbfgs: EXPERIMENT knob active on this context (MI355_DEBUG_GENERAL_KERNEL): the lean solve "
+                         "kernels are never picked; results are unchanged\n");
   *out = ctx;
   return MI355_OK;
 }
@@ -920,6 +924,12 @@ int mi355_lbfgs_last_launch(mi355_lbfgs_ctx* ctx, int32_t* lanes_per_problem, in
   if (threads) *threads = ctx->last_threads;
   if (lds_bytes) *lds_bytes = ctx->last_lds;
   if (y_columns_in_registers) *y_columns_in_registers = ctx->last_mr;
+  return MI355_OK;
+}
+
+int mi355_lbfgs_last_kernel_variant(mi355_lbfgs_ctx* ctx, int32_t* variant) {
+  if (!ctx || !variant) return fail(MI355_ERR_INVALID_ARGUMENT, "null argument");
+  *variant = ctx->last_variant;
   return MI355_OK;
 }
 

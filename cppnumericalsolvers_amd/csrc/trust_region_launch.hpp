@@ -40,6 +40,7 @@ int launch_trust_region(mi355_lbfgs_ctx* ctx, SolveArgs args, const TrustRegionD
   ctx->last_threads = kWave;
   ctx->last_lds = lds;
   ctx->last_mr = 0;
+  ctx->last_variant = MI355_KERNEL_GENERAL;
   ctx->last_arith = MI355_ARITH_EXACT;
   return MI355_OK;
 }

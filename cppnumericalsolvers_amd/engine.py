@@ -406,6 +406,10 @@ class BatchedLbfgs:
         out = dict(zip(("lanes_per_problem", "elems_per_lane", "blocks", "threads", "lds_bytes",
                         "y_columns_in_registers"),
                        [t.value for t in v]))
+        # "lean": the solve kernel with the call's options fixed at compile time (csrc/dispatch_lean.hip); same bits
+        k = C.c_int32()
+        capi.check(self.ctx._lib.mi355_lbfgs_last_kernel_variant(self.ctx.handle, C.byref(k)))
+        out["kernel"] = {0: "general", 1: "lean"}[k.value]
         return out
 
 

@@ -424,6 +424,13 @@ int mi355_lbfgs_last_launch(mi355_lbfgs_ctx* ctx, int32_t* lanes_per_problem,
 int mi355_lbfgs_hessian_condition(const double* hessian, int32_t n, double* condition_out);
 /* The mi355_arithmetic (MI355_ARITH_EXACT or MI355_ARITH_FMA) the most recent solve on this context ran with. */
 int mi355_lbfgs_last_arithmetic(mi355_lbfgs_ctx* ctx, int32_t* arithmetic);
+/* Which build of the solve kernel the most recent solve on this context ran: MI355_KERNEL_GENERAL (every option of the call
+ * is a kernel argument) or MI355_KERNEL_LEAN (the options of a plain First-mode solve fixed at compile time: no trace,
+ * preconditioner, problem map or plateau ring, f_delta test off, relative gradient test; Rosenbrock with n = 32 or 64 filling
+ * its segment, fused arithmetic, m = 6..10).  Both return the same bits. */
+#define MI355_KERNEL_GENERAL 0
+#define MI355_KERNEL_LEAN 1
+int mi355_lbfgs_last_kernel_variant(mi355_lbfgs_ctx* ctx, int32_t* variant);
 
 /* One Hager-Zhang line search per problem: replaces HagerZhang<F, Ord>::Search, State overload
  * (linesearch/hager_zhang.h:100-116), i.e. hzls (:282-548) from x[b] along direction[b] with the
