@@ -16,6 +16,7 @@ int launch_ridge_mfma_mapping(mi355_lbfgs_ctx* ctx, SolveArgs args, hipStream_t 
   if (per_cu < 1) per_cu = 1;
   const long long blocks_needed = (args.B + kJointSlots - 1) / kJointSlots;
   long long blocks_ll = static_cast<long long>(per_cu) * ctx->num_cus;
+  if (ctx->debug_blocks >= 1 && ctx->debug_blocks < blocks_ll) blocks_ll = ctx->debug_blocks;
   if (blocks_ll > blocks_needed) blocks_ll = blocks_needed;
   // plateau rings: MAX_PAST doubles per resident problem slot
   const size_t need = static_cast<size_t>(blocks_ll) * kJointSlots * MI355_LBFGS_MAX_PAST;

@@ -73,7 +73,9 @@ struct mi355_lbfgs_ctx {
   int last_variant = 0;  // MI355_KERNEL_GENERAL / MI355_KERNEL_LEAN: what launch_solve ran (mi355_lbfgs_last_kernel_variant)
   // experiment knobs, read ONCE from the environment when the context is created (mi355_lbfgs_create prints a notice
   // when one is set; 0 = not set): MI355_DEBUG_SOLVE_WAVES caps the wavefronts of a workgroup, MI355_DEBUG_SOLVE_BLOCKS
-  // the resident grid; neither changes a result (scripts/ and profiles/ say where they were used)
+  // the resident grid of EVERY persistent launch (launch_solve, launch_lbfgsb, launch_lbfgsb_fast, launch_wide,
+  // launch_ridge_mfma, launch_trust_region); neither changes a result (scripts/ and profiles/ say where they were used;
+  // tests/test_gpu_work_queue.py holds the capped grid to that, bit for bit)
   int debug_waves = 0;
   long long debug_blocks = 0;
   int debug_general_kernel = 0;  // MI355_DEBUG_GENERAL_KERNEL: never pick the lean solve kernels (A/B runs on one library)
@@ -600,6 +602,7 @@ int launch_lbfgsb(mi355_lbfgs_ctx* ctx, LbfgsbArgs args, hipStream_t stream, con
   if (per_cu < 1) per_cu = 1;
   const long long blocks_needed = (args.s.B + kSegs - 1) / kSegs;
   long long blocks_ll = static_cast<long long>(per_cu) * ctx->num_cus;
+  if (ctx->debug_blocks >= 1 && ctx->debug_blocks < blocks_ll) blocks_ll = ctx->debug_blocks;
   if (blocks_ll > blocks_needed) blocks_ll = blocks_needed;
   args.s.next_problem = ctx->queue_dev;
 #ifdef MI355_LBFGSB_PHASE_TIMING

@@ -26,6 +26,7 @@ int launch_wide(mi355_lbfgs_ctx* ctx, WideArgs args, hipStream_t stream) {
   if (T == kWideThreadsBig) per_cu = 1;
   args.ws_stride = wide_ws_doubles(args.n, args.m, E);
   long long blocks = static_cast<long long>(per_cu) * ctx->num_cus;
+  if (ctx->debug_blocks >= 1 && ctx->debug_blocks < blocks) blocks = ctx->debug_blocks;
   if (blocks > args.B) blocks = args.B;
   // the workspace is (5 + 2m) n doubles per RESIDENT workgroup: keep it under a quarter of the device memory
   if (ctx->device_total_bytes == 0) {   // (asked once per context: hipMemGetInfo synchronises)

@@ -21,6 +21,7 @@ int launch_lbfgsb_fast(mi355_lbfgs_ctx* ctx, LbfgsbArgs args, hipStream_t stream
   if (per_cu < 1) per_cu = 1;
   const long long blocks_needed = (args.s.B + kSegs - 1) / kSegs;
   long long blocks_ll = static_cast<long long>(per_cu) * ctx->num_cus;
+  if (ctx->debug_blocks >= 1 && ctx->debug_blocks < blocks_ll) blocks_ll = ctx->debug_blocks;
   if (blocks_ll > blocks_needed) blocks_ll = blocks_needed;
   args.s.next_problem = ctx->queue_dev;
 #ifdef MI355_LBFGSB_PHASE_TIMING

@@ -257,16 +257,32 @@ __device__ __forceinline__ double vmax_abs(double a, double b) {
   asm("v_max_f64 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
+// max(|a|, 0) / max(a, 0) as one instruction (inline constant): maxNum returns the other operand for a NaN, so a NaN
+// becomes 0 — the `m = 0; if (m < t) m = t` fold of the reference's lpNorm<Infinity> stand-in and of every CPU twin
+__device__ __forceinline__ double vmax_abs_zero(double a) {
+  double r;
+  asm("v_max_f64 %0, |%1|, 0" : "=v"(r) : "v"(a));
+  return r;
+}
+__device__ __forceinline__ double vmax_zero(double a) {
+  double r;
+  asm("v_max_f64 %0, %1, 0" : "=v"(r) : "v"(a));
+  return r;
+}
+// max |a_j| over the segment, 0 when EVERY coordinate is NaN (maxNum alone would return NaN then: with a problem that
+// fills all W x E coordinates no padding lane contributes its 0, and a kernel without a non-finite bail-out — dense
+// BFGS — never saw its gradient test fire where the twin's does)
 template <int W, int E>
 __device__ __forceinline__ double seg_amax(const double (&a)[E]) {
   double m;
   if constexpr (E == 1) {
-    m = vmax_abs(a[0], a[0]);
+    m = vmax_abs_zero(a[0]);
   } else {
     m = vmax_abs(a[0], a[1]);
 #pragma unroll
     for (int e = 2; e + 1 < E; e += 2) m = vmax(m, vmax_abs(a[e], a[e + 1]));
     if constexpr (E % 2 == 1) m = vmax(m, vmax_abs(a[E - 1], a[E - 1]));
+    m = vmax_zero(m);
   }
   return seg_max<W>(m);
 }
