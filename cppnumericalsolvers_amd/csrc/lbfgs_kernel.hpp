@@ -60,8 +60,11 @@ namespace mi355 {
     lphase_t0 = now_;                                               \
     lphase_cur = (i);                                               \
   } while (0)
+// the More-Thuente search charges its trials after the first to phase 11 through this clock
+#define MI355_LPHASE_CLOCK , &lphase_clock
 #else
 #define MI355_LPHASE(i) do { } while (0)
+#define MI355_LPHASE_CLOCK
 #endif
 
 struct TraceArgs {                    // device-resident description of an active trace
@@ -405,6 +408,7 @@ __global__ __launch_bounds__((64 * solve_max_waves<W, E, OUTER, Obj>())) void lb
   for (int i = 0; i < 12; ++i) lphase_cycles[i] = 0;
   unsigned long long lphase_t0 = __builtin_readcyclecounter();
   int lphase_cur = 8;  // kernel prologue
+  [[maybe_unused]] const MtPhaseClock lphase_clock{lphase_cycles, &lphase_t0, &lphase_cur};
 #endif
   // Solver::Minimize prologue from the point in x: evaluate (solver.h:189-192), reset the solver and its Progress
   [[maybe_unused]] double f_start = 0.0;  // that first evaluation (an outer loop reports against it)
@@ -760,8 +764,11 @@ __global__ __launch_bounds__((64 * solve_max_waves<W, E, OUTER, Obj>())) void lb
     if constexpr (LS == MI355_LS_HAGER_ZHANG) {
       double stp = alpha_init;
       nfev += hz_search<W, E, AR>(obj, x, f, g, stp, d, dginit, n, sl, ls_failed);
+    } else if constexpr (OPT::kFixed) {
+      // the lean kernels: first trial peeled, xp doubles as the search's start point (more_thuente_device.hpp)
+      nfev += mt_cvsrch_peeled<W, E, Obj, AR>(obj, x, f, g, alpha_init, d, dginit, xp, n, sl MI355_LPHASE_CLOCK);
     } else {
-      nfev += mt_cvsrch<W, E, Obj, AR>(obj, x, f, g, alpha_init, d, dginit, n, sl);
+      nfev += mt_cvsrch<W, E, Obj, AR>(obj, x, f, g, alpha_init, d, dginit, n, sl MI355_LPHASE_CLOCK);
     }
     if constexpr (LS == MI355_LS_HAGER_ZHANG) {
       if (ls_failed) {  // hzls returned -1: the State overload hands back the start state (hager_zhang.h:100-116)

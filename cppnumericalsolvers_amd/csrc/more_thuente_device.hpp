@@ -272,6 +272,34 @@ __device__ __forceinline__ StepInterval mt_cstep(StepInterval in, const double f
 
 #endif
 
+// Profiling build (-DMI355_LBFGS_PHASE_TIMING): the caller's phase clock, so that the trials after the first are charged
+// to a phase of their own (scripts/lbfgs_phases.py).  Nothing of it exists in any other build.
+// The kernel reports the clock of lane 0 of each wavefront, so the switch must be taken by lane 0 whenever ANY segment
+// of the wavefront goes on to a later trial — also when lane 0's own segment is done and only waits for the others.
+// It therefore stands where every segment that ran the first trial is still active (before the divergent exit), under
+// a ballot of "this segment continues".  (A segment that returned at once, dginit >= 0, is not there; if it is segment
+// 0 the later trials of that pass stay charged to the first-trial phase.  That does not occur on the flagship batches.)
+#ifdef MI355_LBFGS_PHASE_TIMING
+struct MtPhaseClock {
+  unsigned long long* cycles;
+  unsigned long long* t0;
+  int* cur;
+};
+#define MI355_MT_PHASE_PARAM , const MtPhaseClock* phase_clock = nullptr
+#define MI355_MT_PHASE_LATER_IF_ANY(continues)                        \
+  do {                                                                \
+    if (phase_clock != nullptr && __builtin_amdgcn_ballot_w64(continues) != 0) { \
+      const unsigned long long now_ = __builtin_readcyclecounter();   \
+      phase_clock->cycles[*phase_clock->cur] += now_ - *phase_clock->t0; \
+      *phase_clock->t0 = now_;                                        \
+      *phase_clock->cur = 11;                                         \
+    }                                                                 \
+  } while (0)
+#else
+#define MI355_MT_PHASE_PARAM
+#define MI355_MT_PHASE_LATER_IF_ANY(continues) do { } while (0)
+#endif
+
 // more_thuente.h:137-256 with the State-overload prologue of :120-135.
 // In:  x = start point, f/g = value/gradient there, d = NEGATED search direction
 //      (the line search runs along s = -d, lbfgs.h:231-232), stp = initial step,
@@ -283,7 +311,7 @@ __device__ __forceinline__ StepInterval mt_cstep(StepInterval in, const double f
 template <int W, int E, class Obj, class AR = ArithExact>
 __device__ __forceinline__ int mt_cvsrch(const Obj& obj, double (&x)[E], double& f, double (&g)[E],
                                          double stp, const double (&d)[E], const double dginit,
-                                         int n, int sl) {
+                                         int n, int sl MI355_MT_PHASE_PARAM) {
   int info = 0;
   int infoc = 1;
   constexpr double xtol = 1e-15;
@@ -350,6 +378,7 @@ __device__ __forceinline__ int mt_cvsrch(const Obj& obj, double (&x)[E], double&
     if (nfev >= maxfev) info = 3;
     if (brackt & (stmax - stmin <= xtol * stmax)) info = 2;
     if ((f <= ftest1) & (__builtin_fabs(dg) <= gtol * (-dginit))) info = 1;
+    MI355_MT_PHASE_LATER_IF_ANY(info == 0);
     if (info != 0) break;
 
     if (stage1 & (f <= ftest1) & (dg >= dmin(ftol, gtol) * dginit)) stage1 = false;
@@ -383,6 +412,125 @@ __device__ __forceinline__ int mt_cvsrch(const Obj& obj, double (&x)[E], double&
 #pragma unroll
   for (int e = 0; e < E; ++e) x[e] = AR::nmadd(stp, d[e], wa[e]);
 #endif
+  return nfev;
+}
+
+// The same search for the lean solve kernels (OPT::kFixed, lbfgs_kernel.hpp): the first trial peeled out of the loop.
+// Four line searches in five end at their first trial, and the segments of a wavefront run the loop above until the
+// last of them has left it, so the general trip — written for any (brackt, stx, nfev, infoc) — is what every
+// segment pays every iteration.  In the first trip brackt = false, stx = sty = 0, nfev = 0 and infoc = 1 are known:
+//   stmin = stx = 0 and stmax = stp + xtrapf * (stp - 0) (stp - 0.0 is stp, bit for bit, for every stp);
+//   the `stp = stx` fallback and info 6 / 3 / 2 cannot fire (no bracket, nfev = 1 < maxfev, infoc = 1);
+//   info 5, 4, 1 are tested in the reference's order (a later test overwrites an earlier one).
+// Segments with info == 0 then enter the loop, rotated so that it starts at the step computation (cstep) the general
+// trip ends with: stage1, cstep, bracket bookkeeping, then interval / clamp / trial / tests — every expression is the
+// one of the loop above, on the same operands, in the same order, so x, f, g and nfev are the same bits.  The loop
+// sits under one branch that a wavefront skips when none of its segments continues.
+// wa: the start point (the caller's copy of x that it keeps for s = x+ - x; x itself is only written at the end).
+template <int W, int E, class Obj, class AR = ArithExact>
+__device__ __forceinline__ int mt_cvsrch_peeled(const Obj& obj, double (&x)[E], double& f, double (&g)[E],
+                                                double stp, const double (&d)[E], const double dginit,
+                                                const double (&wa)[E], int n, int sl MI355_MT_PHASE_PARAM) {
+  constexpr double xtol = 1e-15;
+  constexpr double ftol = 1e-4;
+  constexpr double gtol = 0.9;
+  constexpr double stpmin = 1e-15;
+  constexpr double stpmax = 1e15;
+  constexpr double xtrapf = 4.0;
+  constexpr int maxfev = 20;
+#ifdef MI355_NO_XRECOMP
+#error "mt_cvsrch_peeled always re-forms the accepted point (it has no -DMI355_NO_XRECOMP form)"
+#endif
+
+  if (dginit >= 0.0) return 0;  // no descent direction: x, f, g untouched (:152-156)
+
+  const double finit = f;
+  const double dgtest = ftol * dginit;
+  // ---- first trial: brackt = false, stx = 0, nfev = 0, infoc = 1 ------------------------------------
+  double stmin = 0.0;
+  double stmax = stp + xtrapf * stp;
+  stp = dclamp(stp, stpmin, stpmax);
+  {
+    double xt[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) xt[e] = AR::nmadd(stp, d[e], wa[e]);  // wa + stp * s
+    f = obj_eval<W, E, AR>(obj, xt, g, n, sl);
+  }
+  int nfev = 1;
+  double dg = -seg_dot<W, E, AR>(g, d);  // g.s
+  double ftest1 = finit + stp * dgtest;
+  int info = 0;
+  if ((stp == stpmax) & (f <= ftest1) & (dg <= dgtest)) info = 5;
+  if ((stp == stpmin) & ((f > ftest1) | (dg >= dgtest))) info = 4;
+  if ((f <= ftest1) & (__builtin_fabs(dg) <= gtol * (-dginit))) info = 1;
+
+  MI355_MT_PHASE_LATER_IF_ANY(info == 0);
+  if (info == 0) {
+    // ---- later trials: the loop of mt_cvsrch, entered at its step computation -----------------------
+    int infoc = 1;
+    bool brackt = false;
+    bool stage1 = true;
+    double width = stpmax - stpmin;
+    double width1 = 2.0 * width;
+    double stx = 0.0, fx = finit, dgx = dginit;
+    double sty = 0.0, fy = finit, dgy = dginit;
+    do {
+      if (stage1 & (f <= ftest1) & (dg >= dmin(ftol, gtol) * dginit)) stage1 = false;
+
+      const bool modified = stage1 & (f <= fx) & (f > ftest1);
+      StepInterval iv;
+      iv.stx = stx; iv.sty = sty; iv.stp = stp; iv.brackt = brackt; iv.info = infoc; iv.rc = 0;
+      iv.fx = modified ? fx - stx * dgtest : fx;
+      iv.fy = modified ? fy - sty * dgtest : fy;
+      iv.dx = modified ? dgx - dgtest : dgx;
+      iv.dy = modified ? dgy - dgtest : dgy;
+      const double fm = modified ? f - stp * dgtest : f;
+      const double dgm = modified ? dg - dgtest : dg;
+      iv = mt_cstep(iv, fm, dgm, stmin, stmax);
+      stx = iv.stx; sty = iv.sty; stp = iv.stp; brackt = iv.brackt; infoc = iv.info;
+      fx = modified ? iv.fx + stx * dgtest : iv.fx;
+      fy = modified ? iv.fy + sty * dgtest : iv.fy;
+      dgx = modified ? iv.dx + dgtest : iv.dx;
+      dgy = modified ? iv.dy + dgtest : iv.dy;
+      if (brackt) {
+        if (__builtin_fabs(sty - stx) >= 0.66 * width1) stp = stx + 0.5 * (sty - stx);
+        width1 = width;
+        width = __builtin_fabs(sty - stx);
+      }
+
+      if (brackt) {
+        stmin = dmin(stx, sty);
+        stmax = dmax(stx, sty);
+      } else {
+        stmin = stx;
+        stmax = stp + xtrapf * (stp - stx);
+      }
+      stp = dclamp(stp, stpmin, stpmax);
+      if ((brackt && ((stp <= stmin) || (stp >= stmax))) || (nfev >= maxfev - 1) || (infoc == 0) ||
+          (brackt && ((stmax - stmin) <= (xtol * stmax)))) {
+        stp = stx;
+      }
+      {
+        double xt[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) xt[e] = AR::nmadd(stp, d[e], wa[e]);  // wa + stp * s
+        f = obj_eval<W, E, AR>(obj, xt, g, n, sl);
+      }
+      nfev++;
+      dg = -seg_dot<W, E, AR>(g, d);  // g.s
+      ftest1 = finit + stp * dgtest;
+
+      if ((brackt & ((stp <= stmin) | (stp >= stmax))) | (infoc == 0)) info = 6;
+      if ((stp == stpmax) & (f <= ftest1) & (dg <= dgtest)) info = 5;
+      if ((stp == stpmin) & ((f > ftest1) | (dg >= dgtest))) info = 4;
+      if (nfev >= maxfev) info = 3;
+      if (brackt & (stmax - stmin <= xtol * stmax)) info = 2;
+      if ((f <= ftest1) & (__builtin_fabs(dg) <= gtol * (-dginit))) info = 1;
+    } while (info == 0);
+  }
+  // the accepted point, re-formed from the accepted step: same operands, same bits
+#pragma unroll
+  for (int e = 0; e < E; ++e) x[e] = AR::nmadd(stp, d[e], wa[e]);
   return nfev;
 }
 
