@@ -85,6 +85,18 @@ class TrustRegionConfig(C.Structure):
                 ("rejection_retry_limit", C.c_int32)]
 
 
+# ... and the Nelder-Mead solver's (checked by tests/test_nelder_mead_twin.py)
+NELDER_MEAD_SYMBOLS = ["mi355_nelder_mead_default_config", "mi355_nelder_mead_minimize_batch",
+                       "mi355_nelder_mead_minimize_batch_host"]
+NM_MODE_VALUE, NM_MODE_FIRST = 0, 1
+
+
+class NelderMeadConfig(C.Structure):
+    """mi355_nelder_mead_config: the coefficients of the reference's NelderMead and the mode."""
+    _fields_ = [("rho", C.c_double), ("xi", C.c_double), ("gamma", C.c_double), ("sigma", C.c_double),
+                ("degenerate_tol", C.c_double), ("mode", C.c_int32)]
+
+
 class Desc(C.Structure):
     """mi355_lbfgs_desc."""
     _fields_ = [
@@ -225,6 +237,11 @@ def _bind(L):
                                                            vp, vp, vp, vp, vp, vp]
     L.mi355_trust_region_newton_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), C.POINTER(TrustRegionConfig),
                                                                 C.c_int64, vp, vp, vp, vp, vp]
+    L.mi355_nelder_mead_default_config.argtypes = [C.POINTER(NelderMeadConfig)]
+    L.mi355_nelder_mead_minimize_batch.argtypes = [vp, C.POINTER(Desc), C.POINTER(NelderMeadConfig), C.c_int64,
+                                                   vp, vp, vp, vp, vp, vp]
+    L.mi355_nelder_mead_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), C.POINTER(NelderMeadConfig), C.c_int64,
+                                                        vp, vp, vp, vp, vp]
     L.mi355_lbfgsb_minimize_batch.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mi355_lbfgsb_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, vp, vp, vp, vp, vp]
     L.mi355_lbfgs_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -286,6 +303,21 @@ def default_trust_region_config(**overrides):
     for k, v in overrides.items():
         if not hasattr(c, k):
             raise TypeError("TrustRegionNewtonConfig has no field %r" % k)
+        setattr(c, k, v)
+    return c
+
+
+def default_nelder_mead_config(**overrides):
+    """mi355_nelder_mead_default_config(), with the named fields replaced (mode: "value" / "first" or the id)."""
+    c = NelderMeadConfig()
+    check(load().mi355_nelder_mead_default_config(C.byref(c)))
+    for k, v in overrides.items():
+        if not hasattr(c, k):
+            raise TypeError("NelderMead config has no field %r" % k)
+        if k == "mode" and isinstance(v, str):
+            if v not in ("value", "first"):
+                raise ValueError("mode must be 'value' or 'first'")
+            v = NM_MODE_FIRST if v == "first" else NM_MODE_VALUE
         setattr(c, k, v)
     return c
 

@@ -1,0 +1,26 @@
+// dispatch_nelder_mead.hip — the kernels of mi355_nelder_mead_minimize_batch (nelder_mead_kernel.hpp): one coordinate
+// per lane at 8, 16, 32 or 64 lanes per problem, value mode and first mode, on Rosenbrock and DiagQuadratic.  User
+// functors get their own units (_build.py, nelder_mead=True).
+#define MI355_DISPATCH_TU 1
+#include "engine_internal.hpp"
+#include "nelder_mead_launch.hpp"
+
+namespace mi355 {
+
+int dispatch_nelder_mead(mi355_lbfgs_ctx* ctx, int W, int objective, const SolveArgs& args,
+                         const NelderMeadDeviceConfig& cfg, hipStream_t stream) {
+  switch (objective) {
+    case MI355_OBJ_ROSENBROCK:
+      return launch_nelder_mead_w<RosenbrockObjective>(ctx, W, args, cfg, stream);
+    case MI355_OBJ_DIAG_QUADRATIC:
+      return launch_nelder_mead_w<DiagQuadraticObjective<1>>(ctx, W, args, cfg, stream);
+  }
+  if (objective >= MI355_OBJ_USER_FIRST) {
+    const UserNelderMeadFn fn = user_nelder_mead(objective);
+    if (fn != nullptr) return fn(ctx, W, args, cfg, stream);
+  }
+  return fail(MI355_ERR_INVALID_ARGUMENT,
+              "NelderMead is built for Rosenbrock, DiagQuadratic and user functors built with nelder_mead=True");
+}
+
+}  // namespace mi355

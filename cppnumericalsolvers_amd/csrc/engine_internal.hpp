@@ -17,6 +17,7 @@
 #include "../../include/mi355_lbfgs.h"
 #include "lbfgs_kernel.hpp"
 #include "lbfgsb_kernel.hpp"
+#include "nelder_mead_config.hpp"
 #include "trust_region_config.hpp"
 
 constexpr int kQueueWords = 4;  // work-queue head (+ spare words), zeroed before every launch
@@ -214,6 +215,18 @@ void register_user_trust_region(int objective_id, UserTrustRegionFn fn);
 UserTrustRegionFn user_trust_region(int objective_id);
 struct UserTrustRegionRegistration {
   UserTrustRegionRegistration(int objective_id, UserTrustRegionFn fn) { register_user_trust_region(objective_id, fn); }
+};
+
+// NelderMead (dispatch_nelder_mead.hip, nelder_mead_kernel.hpp): W lanes per problem, one coordinate per lane
+int dispatch_nelder_mead(mi355_lbfgs_ctx* ctx, int W, int objective, const SolveArgs& args,
+                         const NelderMeadDeviceConfig& cfg, hipStream_t stream);
+// ... on a user functor with a value entry: registered by the unit _build.py generates for nelder_mead=True
+using UserNelderMeadFn = int (*)(mi355_lbfgs_ctx* ctx, int W, const SolveArgs& args, const NelderMeadDeviceConfig& cfg,
+                                 hipStream_t stream);
+void register_user_nelder_mead(int objective_id, UserNelderMeadFn fn);
+UserNelderMeadFn user_nelder_mead(int objective_id);
+struct UserNelderMeadRegistration {
+  UserNelderMeadRegistration(int objective_id, UserNelderMeadFn fn) { register_user_nelder_mead(objective_id, fn); }
 };
 
 // desc->trace (device array pointers) -> the trace fields of SolveArgs; uploads the problem list, zeroes `written`

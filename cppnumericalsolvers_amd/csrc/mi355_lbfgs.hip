@@ -29,6 +29,7 @@ struct UserEntry {
   UserDispatchFn fn[4] = {nullptr, nullptr, nullptr, nullptr};  // lanes per problem 8, 16, 32, 64
   UserLbfgsbFn lbfgsb = nullptr;
   UserTrustRegionFn trust_region = nullptr;
+  UserNelderMeadFn nelder_mead = nullptr;
   std::string name;
 };
 std::vector<std::pair<int, UserEntry>>& user_table() {
@@ -77,6 +78,23 @@ void register_user_trust_region(int objective_id, UserTrustRegionFn fn) {
 UserTrustRegionFn user_trust_region(int objective_id) {
   for (auto& e : user_table())
     if (e.first == objective_id) return e.second.trust_region;
+  return nullptr;
+}
+void register_user_nelder_mead(int objective_id, UserNelderMeadFn fn) {
+  if (objective_id < MI355_OBJ_USER_FIRST) return;
+  for (auto& e : user_table()) {
+    if (e.first == objective_id) {
+      e.second.nelder_mead = fn;
+      return;
+    }
+  }
+  UserEntry u;
+  u.nelder_mead = fn;
+  user_table().emplace_back(objective_id, u);
+}
+UserNelderMeadFn user_nelder_mead(int objective_id) {
+  for (auto& e : user_table())
+    if (e.first == objective_id) return e.second.nelder_mead;
   return nullptr;
 }
 static const UserEntry* find_user_objective(int objective_id) {
@@ -1305,4 +1323,88 @@ extern "C" int mi355_trust_region_newton_minimize_batch(mi355_lbfgs_ctx* ctx, co
   rc = setup_trace(ctx, &desc, B, stream, args);
   if (rc != MI355_OK) return rc;
   return dispatch_trust_region(ctx, W, desc.objective, args, dc, stream);
+}
+
+// ---- NelderMead (nelder_mead_kernel.hpp) ---------------------------------------------------------------------------
+extern "C" int mi355_nelder_mead_default_config(mi355_nelder_mead_config* out) {
+  if (!out) return fail(MI355_ERR_INVALID_ARGUMENT, "null config");
+  out->rho = 1.0;             // nelder_mead.h:58-64
+  out->xi = 20.0;
+  out->gamma = 0.1;
+  out->sigma = 0.5;
+  out->degenerate_tol = 1e-8;
+  out->mode = MI355_NM_MODE_VALUE;
+  return MI355_OK;
+}
+
+extern "C" int mi355_nelder_mead_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc_in,
+                                                const mi355_nelder_mead_config* config, int64_t B, const double* x0,
+                                                double* x_out, double* f_out, double* g_out,
+                                                mi355_lbfgs_progress* progress_out, void* stream_) {
+  if (!desc_in) return fail(MI355_ERR_INVALID_ARGUMENT, "null desc");
+  // m, the line search and every Hessian field mean nothing to a derivative-free solver
+  mi355_lbfgs_desc desc = *desc_in;
+  desc.m = 1;
+  desc.linesearch = MI355_LS_MORE_THUENTE;
+  desc.history_placement = 0;
+  desc.hessian_diagonal = nullptr;
+  desc.hessian_from_functor = 0;
+  desc.hessian_condition_stop = 0.0;
+  if (desc.n > 64)
+    return fail(MI355_ERR_INVALID_ARGUMENT, "NelderMead is built for n <= 64 (the simplex is n x (n + 1) in LDS per problem)");
+  if (desc.objective != MI355_OBJ_ROSENBROCK && desc.objective != MI355_OBJ_DIAG_QUADRATIC &&
+      !(desc.objective >= MI355_OBJ_USER_FIRST && user_nelder_mead(desc.objective) != nullptr))
+    return fail(MI355_ERR_INVALID_ARGUMENT,
+                desc.objective >= MI355_OBJ_USER_FIRST
+                    ? "NelderMead: this library holds no Nelder-Mead kernel for this user objective (build it with "
+                      "nelder_mead=True and a functor that defines value)"
+                    : "NelderMead is built for Rosenbrock, DiagQuadratic and user functors built with nelder_mead=True");
+  if (desc.arithmetic == MI355_ARITH_FMA)
+    return fail(MI355_ERR_INVALID_ARGUMENT, "NelderMead is built for the exact arithmetic only (no MI355_ARITH_FMA)");
+  int rc = validate(ctx, &desc, B);
+  if (rc != MI355_OK) return rc;
+  if (desc.elems_per_lane != 0 && desc.elems_per_lane != 1)
+    return fail(MI355_ERR_INVALID_ARGUMENT, "NelderMead: one coordinate per lane (elems_per_lane 0 or 1)");
+  int W = desc.lanes_per_problem;
+  if (W == 0) {
+    W = 8;
+    while (W < desc.n) W <<= 1;
+  } else if (!(W == 8 || W == 16 || W == 32 || W == 64) || W < desc.n) {
+    return fail(MI355_ERR_INVALID_ARGUMENT, "NelderMead: lanes_per_problem must be 8, 16, 32 or 64 and cover n");
+  }
+  mi355_nelder_mead_config c;
+  mi355_nelder_mead_default_config(&c);
+  if (config) c = *config;
+  if (c.mode != MI355_NM_MODE_VALUE && c.mode != MI355_NM_MODE_FIRST)
+    return fail(MI355_ERR_INVALID_ARGUMENT, "NelderMead: mode must be MI355_NM_MODE_VALUE or MI355_NM_MODE_FIRST");
+  NelderMeadDeviceConfig dc;
+  dc.rho = c.rho;
+  dc.xi = c.xi;
+  dc.gamma = c.gamma;
+  dc.sigma = c.sigma;
+  dc.degenerate_tol = c.degenerate_tol;
+  dc.first_mode = c.mode == MI355_NM_MODE_FIRST ? 1 : 0;
+  if (B == 0) return MI355_OK;
+  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MI355_ENTER_DEVICE(ctx);
+  rc = upload_params(ctx, &desc, W, 1, stream);
+  if (rc != MI355_OK) return rc;
+  SolveArgs args;
+  std::memset(&args, 0, sizeof(args));
+  args.x0 = x0;
+  args.x_out = x_out;
+  args.f_out = f_out;
+  args.g_out = g_out;
+  args.progress_out = progress_out;
+  args.obj_params = ctx->params_dev;
+  args.per_problem = desc.per_problem_data;
+  args.per_problem_stride = desc.per_problem_stride;
+  args.B = B;
+  args.n = desc.n;
+  args.m = 1;
+  args.stop = desc.stop;
+  rc = setup_trace(ctx, &desc, B, stream, args);
+  if (rc != MI355_OK) return rc;
+  return dispatch_nelder_mead(ctx, W, desc.objective, args, dc, stream);
 }

@@ -49,6 +49,13 @@ struct RosenbrockObjectiveT {
   __device__ __forceinline__ double eval(const double (&x)[E], double (&g)[E], int n, int sl) const {
     return eval_impl<W, E, SEGMENT_FULL>(x, g, n, sl);
   }
+  // The value alone, for the derivative-free kernel (nelder_mead_kernel.hpp): eval with its gradient dropped, so the
+  // terms and their reduction — and the bits of f — are eval's.
+  template <int W, int E>
+  __device__ __forceinline__ double value(const double (&x)[E], int n, int sl) const {
+    double g[E];
+    return eval<W, E>(x, g, n, sl);
+  }
   template <int W, int E, bool FULL>
   __device__ __forceinline__ double eval_impl(const double (&x)[E], double (&g)[E], int n, int sl) const {
     // x_{j+1}: next element in-lane, or element 0 of the next lane.
@@ -218,6 +225,12 @@ struct DiagQuadraticObjective {
       g[e] = (j < n) ? (2.0 * coefficient(e, sl)) * x[e] : 0.0;
     }
     return seg_sum<W>(lane_tree_sum<E>(term)) + constant();
+  }
+  // the value alone (nelder_mead_kernel.hpp): eval with its gradient dropped, the same terms and reduction
+  template <int W, int EE>
+  __device__ __forceinline__ double value(const double (&x)[EE], int n, int sl) const {
+    double g[EE];
+    return eval<W, EE>(x, g, n, sl);
   }
   // fused policy: term_i accumulates as the chain fma(a_i x_i, x_i, previous) over the lane's coordinates
   template <int W, int EE>

@@ -486,6 +486,69 @@ class BatchedTrustRegionNewton(BatchedLbfgs):
         return x, f, g, prog
 
 
+class BatchedNelderMead(BatchedLbfgs):
+    """Batched `NelderMead<F>` (reference solver/nelder_mead.h): the derivative-free simplex method, one problem per
+    wavefront segment with the simplex and its vertex values in LDS; n <= 64, Rosenbrock, DiagQuadratic and user functors
+    built with nelder_mead=True.
+
+    rho, xi, gamma, sigma, degenerate_tol are the reference's coefficients (defaults 1, 20, 0.1, 0.5, 1e-8).  mode="value"
+    is DifferentiabilityMode::None (g comes back as zeros, no gradient test), mode="first" the reference on a First-mode
+    function (value and gradient at the returned vertex, gradient test on).  The default stopping progress is the
+    reference's for this solver: the conservative preset with x_delta_violations = 5."""
+    _entry = "mi355_nelder_mead_minimize_batch"
+
+    def __init__(self, stopping_progress=None, device=0, context=None, lanes_per_problem=0, **config):
+        if stopping_progress is None:
+            stopping_progress = capi.default_stop("conservative")   # nelder_mead.h:87-91
+            stopping_progress.x_delta_violations = 5
+        super().__init__(m=1, stopping_progress=stopping_progress, device=device, context=context,
+                         arithmetic="exact", lanes_per_problem=lanes_per_problem)
+        self.config = capi.default_nelder_mead_config(**config)
+
+    def _desc(self, objective, n, per_problem=None, per_problem_stride=0):
+        d = super()._desc(objective, n, per_problem, per_problem_stride)
+        d.hessian_from_functor = 0
+        d.hessian_diagonal = None
+        d.hessian_condition = 0.0
+        d.hessian_condition_stop = 0.0
+        return d
+
+    def minimize(self, objective, x0, want_gradient=True, want_progress=True, per_problem=None, trace=None):
+        torch = self._torch
+        if x0.dtype != torch.float64 or x0.dim() != 2 or not x0.is_cuda:
+            raise ValueError("x0 must be a [B, n] float64 CUDA tensor")
+        self._on_device(x0, "x0")
+        x0 = x0.contiguous()
+        B, n = x0.shape
+        x = torch.empty_like(x0)
+        f = torch.empty(B, dtype=torch.float64, device=x0.device)
+        g = torch.empty_like(x0) if want_gradient else None
+        prog = torch.empty(B * capi.PROGRESS_DTYPE.itemsize, dtype=torch.uint8, device=x0.device) \
+            if want_progress else None
+        d = self._desc(objective, n, *self._pp_device(per_problem, B))
+        if trace is not None:
+            self._trace_keepalive = trace
+            d.trace = trace.c_pointer()
+        capi.check(self.ctx._lib.mi355_nelder_mead_minimize_batch(
+            self.ctx.handle, C.byref(d), C.byref(self.config), B, x0.data_ptr(), x.data_ptr(), f.data_ptr(),
+            g.data_ptr() if g is not None else None, prog.data_ptr() if prog is not None else None, self._stream()))
+        return x, f, g, prog
+
+    def minimize_host(self, objective, x0, per_problem=None):
+        """Same through the host-pointer entry point (numpy in, numpy out, synchronous)."""
+        if per_problem is not None:
+            raise ValueError("per-problem data: use minimize() with device tensors")
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        B, n = x0.shape
+        x, g, f = np.empty_like(x0), np.empty_like(x0), np.empty(B)
+        prog = np.zeros(B, dtype=capi.PROGRESS_DTYPE)
+        d = self._desc(objective, n)
+        capi.check(self.ctx._lib.mi355_nelder_mead_minimize_batch_host(
+            self.ctx.handle, C.byref(d), C.byref(self.config), B, x0.ctypes.data, x.ctypes.data, f.ctypes.data,
+            g.ctypes.data, prog.ctypes.data))
+        return x, f, g, prog
+
+
 class BatchedLbfgsb(BatchedLbfgs):
     """Batched `Lbfgsb<F, m>` (reference solver/lbfgsb.h, default m = 5; built for m <= 10): box-constrained L-BFGS-B.
 

@@ -411,6 +411,50 @@ int mi355_trust_region_newton_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi
                                                   double* x_out, double* f_out, double* g_out,
                                                   mi355_lbfgs_progress* progress_out);
 
+/* ---- NelderMead -----------------------------------------------------------
+ * The coefficients of cppoptlib::solver::NelderMead (solver/nelder_mead.h:58-64; const members there, fields here) and
+ * the differentiability mode of the function type.  mi355_nelder_mead_default_config() fills the defaults. */
+enum mi355_nelder_mead_mode {
+  MI355_NM_MODE_VALUE = 0, /* DifferentiabilityMode::None: values only; gradient_norm stays 0, no gradient test, g_out zeros */
+  MI355_NM_MODE_FIRST = 1  /* a First-mode function: value and gradient at the returned vertex once per step, and
+                              Progress::Update's gradient test applies */
+};
+typedef struct mi355_nelder_mead_config {
+  double rho;            /* 1: reflection */
+  double xi;             /* 20: expansion */
+  double gamma;          /* 0.1: contraction */
+  double sigma;          /* 0.5: shrink */
+  double degenerate_tol; /* 1e-8: the simplex restarts when no vertex is further than this from the best (inf-norm) */
+  int32_t mode;          /* mi355_nelder_mead_mode */
+} mi355_nelder_mead_config;
+int mi355_nelder_mead_default_config(mi355_nelder_mead_config* out);
+
+/* Nelder-Mead: replaces cppoptlib::solver::NelderMead<FunctionType>::Minimize (nelder_mead.h under Solver::Minimize,
+ * solver/solver.h:181-224) for B problems at once, one problem per segment of a wavefront, the simplex n x (n + 1) and its
+ * vertex values in LDS.  Vertices are ordered by value, equal values by the lower vertex index.  The stopping tests of
+ * Progress::Update (desc->stop; the reference's default for this solver is the conservative preset with
+ * x_delta_violations = 5).  Objectives: Rosenbrock, DiagQuadratic, and user functors built with nelder_mead=True;
+ * n <= 64; exact arithmetic only.  Everything else returns MI355_ERR_INVALID_ARGUMENT with the reason.  desc->m,
+ * linesearch, history_placement and the Hessian fields are ignored.  Mapping: lanes_per_problem 0 = the library's choice
+ * (the padded width of n, at least 8) or 8, 16, 32, 64 >= n; elems_per_lane 0 or 1.  config NULL = the defaults.
+ * The fields of mi355_lbfgs_progress for this solver:
+ *   num_iterations  steps (Progress::num_iterations)
+ *   nfev            the objective calls the reference makes: 1 at the start, then per step n + 1 for the vertices, n + 1
+ *                   more on a restart, 1 for the reflection, 1 for an expansion or contraction, n + 1 on a shrink and 1
+ *                   for the state of the returned vertex (the kernel keeps unmoved vertices' values and evaluates new
+ *                   points only)
+ *   sum_k           0
+ *   x_delta, f_delta, gradient_norm: as for the other solvers, between the returned vertices of consecutive steps. */
+int mi355_nelder_mead_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
+                                     const mi355_nelder_mead_config* config, int64_t B, const double* x0, double* x_out,
+                                     double* f_out, double* g_out, mi355_lbfgs_progress* progress_out, void* stream);
+/* The same with host arrays (g_out and progress_out may be NULL): pinned staging and chunks, as the other _host entry
+ * points; returns when the results are in the host arrays. */
+int mi355_nelder_mead_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
+                                          const mi355_nelder_mead_config* config, int64_t B, const double* x0,
+                                          double* x_out, double* f_out, double* g_out,
+                                          mi355_lbfgs_progress* progress_out);
+
 /* Duration in ms of the most recent solve kernel on this context, measured with
  * HIP events recorded on the launch stream; blocks until that kernel finished. */
 int mi355_lbfgs_last_kernel_ms(mi355_lbfgs_ctx* ctx, float* ms);
