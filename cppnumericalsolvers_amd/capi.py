@@ -97,6 +97,16 @@ class NelderMeadConfig(C.Structure):
                 ("degenerate_tol", C.c_double), ("mode", C.c_int32)]
 
 
+# ... and the Newton-descent solver's (checked by tests/test_newton_descent_twin.py)
+NEWTON_DESCENT_SYMBOLS = ["mi355_newton_descent_default_config", "mi355_newton_descent_minimize_batch",
+                          "mi355_newton_descent_minimize_batch_host"]
+
+
+class NewtonDescentConfig(C.Structure):
+    """mi355_newton_descent_config: the constants of the reference's NewtonDescent and of its Armijo search."""
+    _fields_ = [("safe_guard", C.c_double), ("armijo_c", C.c_double), ("armijo_rho", C.c_double)]
+
+
 class Desc(C.Structure):
     """mi355_lbfgs_desc."""
     _fields_ = [
@@ -242,6 +252,11 @@ def _bind(L):
                                                    vp, vp, vp, vp, vp, vp]
     L.mi355_nelder_mead_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), C.POINTER(NelderMeadConfig), C.c_int64,
                                                         vp, vp, vp, vp, vp]
+    L.mi355_newton_descent_default_config.argtypes = [C.POINTER(NewtonDescentConfig)]
+    L.mi355_newton_descent_minimize_batch.argtypes = [vp, C.POINTER(Desc), C.POINTER(NewtonDescentConfig), C.c_int64,
+                                                      vp, vp, vp, vp, vp, vp]
+    L.mi355_newton_descent_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), C.POINTER(NewtonDescentConfig),
+                                                           C.c_int64, vp, vp, vp, vp, vp]
     L.mi355_lbfgsb_minimize_batch.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mi355_lbfgsb_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, vp, vp, vp, vp, vp]
     L.mi355_lbfgs_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -318,6 +333,17 @@ def default_nelder_mead_config(**overrides):
             if v not in ("value", "first"):
                 raise ValueError("mode must be 'value' or 'first'")
             v = NM_MODE_FIRST if v == "first" else NM_MODE_VALUE
+        setattr(c, k, v)
+    return c
+
+
+def default_newton_descent_config(**overrides):
+    """mi355_newton_descent_default_config(), with the named fields replaced."""
+    c = NewtonDescentConfig()
+    check(load().mi355_newton_descent_default_config(C.byref(c)))
+    for k, v in overrides.items():
+        if not hasattr(c, k):
+            raise TypeError("NewtonDescent config has no field %r" % k)
         setattr(c, k, v)
     return c
 

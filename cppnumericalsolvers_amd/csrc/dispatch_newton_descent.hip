@@ -1,0 +1,30 @@
+// dispatch_newton_descent.hip — the kernels of mi355_newton_descent_minimize_batch (newton_descent_kernel.hpp): one
+// coordinate per lane at 8, 16, 32 or 64 lanes per problem, on the built-in objectives whose functor has a hess_full
+// (Rosenbrock, DiagQuadratic).  User functors with a hess_full get their own units (_build.py, newton_descent=True).
+#define MI355_DISPATCH_TU 1
+#include "engine_internal.hpp"
+#include "newton_descent_launch.hpp"
+
+namespace mi355 {
+
+int dispatch_newton_descent(mi355_lbfgs_ctx* ctx, int W, int objective, const SolveArgs& args,
+                            const NewtonDescentDeviceConfig& cfg, hipStream_t stream) {
+  switch (objective) {
+    case MI355_OBJ_ROSENBROCK:
+      return launch_newton_descent_w<RosenbrockConditionObjective>(ctx, W, args, cfg, stream);
+    case MI355_OBJ_DIAG_QUADRATIC:
+      return launch_newton_descent_w<DiagQuadraticHessObjective<1>>(ctx, W, args, cfg, stream);
+  }
+  if (objective >= MI355_OBJ_USER_FIRST) {
+    const UserNewtonDescentFn fn = user_newton_descent(objective);
+    if (fn != nullptr) return fn(ctx, W, args, cfg, stream);
+    return fail(MI355_ERR_UNSUPPORTED,
+                "NewtonDescent: this library holds no Newton-descent kernel for this user objective (build it with "
+                "newton_descent=True and a functor that defines hess_full)");
+  }
+  return fail(MI355_ERR_UNSUPPORTED,
+              "NewtonDescent is built for objectives with a device Hessian (hess_full): Rosenbrock, DiagQuadratic and "
+              "user functors built with newton_descent=True; the ridge forms and the augmented-Lagrangian composite have none");
+}
+
+}  // namespace mi355

@@ -18,6 +18,7 @@
 #include "lbfgs_kernel.hpp"
 #include "lbfgsb_kernel.hpp"
 #include "nelder_mead_config.hpp"
+#include "newton_descent_config.hpp"
 #include "trust_region_config.hpp"
 
 constexpr int kQueueWords = 4;  // work-queue head (+ spare words), zeroed before every launch
@@ -227,6 +228,20 @@ void register_user_nelder_mead(int objective_id, UserNelderMeadFn fn);
 UserNelderMeadFn user_nelder_mead(int objective_id);
 struct UserNelderMeadRegistration {
   UserNelderMeadRegistration(int objective_id, UserNelderMeadFn fn) { register_user_nelder_mead(objective_id, fn); }
+};
+
+// NewtonDescent (dispatch_newton_descent.hip, newton_descent_kernel.hpp): W lanes per problem, one coordinate per lane
+int dispatch_newton_descent(mi355_lbfgs_ctx* ctx, int W, int objective, const SolveArgs& args,
+                            const NewtonDescentDeviceConfig& cfg, hipStream_t stream);
+// ... on a user functor with a hess_full: registered by the unit _build.py generates for newton_descent=True
+using UserNewtonDescentFn = int (*)(mi355_lbfgs_ctx* ctx, int W, const SolveArgs& args,
+                                    const NewtonDescentDeviceConfig& cfg, hipStream_t stream);
+void register_user_newton_descent(int objective_id, UserNewtonDescentFn fn);
+UserNewtonDescentFn user_newton_descent(int objective_id);
+struct UserNewtonDescentRegistration {
+  UserNewtonDescentRegistration(int objective_id, UserNewtonDescentFn fn) {
+    register_user_newton_descent(objective_id, fn);
+  }
 };
 
 // desc->trace (device array pointers) -> the trace fields of SolveArgs; uploads the problem list, zeroes `written`

@@ -30,6 +30,7 @@ struct UserEntry {
   UserLbfgsbFn lbfgsb = nullptr;
   UserTrustRegionFn trust_region = nullptr;
   UserNelderMeadFn nelder_mead = nullptr;
+  UserNewtonDescentFn newton_descent = nullptr;
   std::string name;
 };
 std::vector<std::pair<int, UserEntry>>& user_table() {
@@ -95,6 +96,23 @@ void register_user_nelder_mead(int objective_id, UserNelderMeadFn fn) {
 UserNelderMeadFn user_nelder_mead(int objective_id) {
   for (auto& e : user_table())
     if (e.first == objective_id) return e.second.nelder_mead;
+  return nullptr;
+}
+void register_user_newton_descent(int objective_id, UserNewtonDescentFn fn) {
+  if (objective_id < MI355_OBJ_USER_FIRST) return;
+  for (auto& e : user_table()) {
+    if (e.first == objective_id) {
+      e.second.newton_descent = fn;
+      return;
+    }
+  }
+  UserEntry u;
+  u.newton_descent = fn;
+  user_table().emplace_back(objective_id, u);
+}
+UserNewtonDescentFn user_newton_descent(int objective_id) {
+  for (auto& e : user_table())
+    if (e.first == objective_id) return e.second.newton_descent;
   return nullptr;
 }
 static const UserEntry* find_user_objective(int objective_id) {
@@ -1407,4 +1425,87 @@ extern "C" int mi355_nelder_mead_minimize_batch(mi355_lbfgs_ctx* ctx, const mi35
   rc = setup_trace(ctx, &desc, B, stream, args);
   if (rc != MI355_OK) return rc;
   return dispatch_nelder_mead(ctx, W, desc.objective, args, dc, stream);
+}
+
+// ---- NewtonDescent (newton_descent_kernel.hpp) ---------------------------------------------------------------------
+extern "C" int mi355_newton_descent_default_config(mi355_newton_descent_config* out) {
+  if (!out) return fail(MI355_ERR_INVALID_ARGUMENT, "null config");
+  out->safe_guard = 1e-5;   // newton_descent.h:69
+  out->armijo_c = 0.2;      // linesearch/armijo.h:85-86
+  out->armijo_rho = 0.9;
+  return MI355_OK;
+}
+
+extern "C" int mi355_newton_descent_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc_in,
+                                                   const mi355_newton_descent_config* config, int64_t B,
+                                                   const double* x0, double* x_out, double* f_out, double* g_out,
+                                                   mi355_lbfgs_progress* progress_out, void* stream_) {
+  if (!desc_in) return fail(MI355_ERR_INVALID_ARGUMENT, "null desc");
+  // m and the line search field mean nothing to this solver; the Hessian always comes from the functor
+  mi355_lbfgs_desc desc = *desc_in;
+  desc.m = 1;
+  desc.linesearch = MI355_LS_MORE_THUENTE;
+  desc.history_placement = 0;
+  if (desc.hessian_diagonal != nullptr)
+    return fail(MI355_ERR_INVALID_ARGUMENT, "NewtonDescent: H(x) comes from the device functor (hessian_diagonal NULL)");
+  desc.hessian_from_functor = 1;
+  if (desc.n > 64)
+    return fail(MI355_ERR_UNSUPPORTED, "NewtonDescent is built for n <= 64 (H and its LU are n x n in LDS per problem)");
+  int rc = validate(ctx, &desc, B);
+  if (rc != MI355_OK) return rc;
+  if (desc.arithmetic == MI355_ARITH_FMA)
+    return fail(MI355_ERR_UNSUPPORTED, "NewtonDescent is built for the exact arithmetic only (no MI355_ARITH_FMA)");
+  if (desc.objective != MI355_OBJ_ROSENBROCK && desc.objective != MI355_OBJ_DIAG_QUADRATIC &&
+      !(desc.objective >= MI355_OBJ_USER_FIRST && user_newton_descent(desc.objective) != nullptr))
+    return fail(MI355_ERR_UNSUPPORTED,
+                desc.objective >= MI355_OBJ_USER_FIRST
+                    ? "NewtonDescent: this library holds no Newton-descent kernel for this user objective (build it with "
+                      "newton_descent=True and a functor that defines hess_full)"
+                    : "NewtonDescent is built for objectives with a device Hessian (hess_full): Rosenbrock, "
+                      "DiagQuadratic and user functors; the ridge forms, the augmented-Lagrangian composite and sum / "
+                      "product records have none");
+  if (desc.elems_per_lane != 0 && desc.elems_per_lane != 1)
+    return fail(MI355_ERR_INVALID_ARGUMENT, "NewtonDescent: one coordinate per lane (elems_per_lane 0 or 1)");
+  int W = desc.lanes_per_problem;
+  if (W == 0) {
+    // the padded width, except 16 < n <= 32: 64 lanes measured faster there (one problem per wavefront halves the LDS
+    // per wavefront; profiles/newton_descent_bench.jsonl)
+    W = 8;
+    while (W < desc.n) W <<= 1;
+    if (W == 32) W = 64;
+  } else if (!(W == 8 || W == 16 || W == 32 || W == 64) || W < desc.n) {
+    return fail(MI355_ERR_INVALID_ARGUMENT, "NewtonDescent: lanes_per_problem must be 8, 16, 32 or 64 and cover n");
+  }
+  mi355_newton_descent_config c;
+  mi355_newton_descent_default_config(&c);
+  if (config) c = *config;
+  NewtonDescentDeviceConfig dc;
+  dc.safe_guard = c.safe_guard;
+  dc.armijo_c = c.armijo_c;
+  dc.armijo_rho = c.armijo_rho;
+  if (B == 0) return MI355_OK;
+  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MI355_ENTER_DEVICE(ctx);
+  rc = upload_params(ctx, &desc, W, 1, stream);
+  if (rc != MI355_OK) return rc;
+  SolveArgs args;
+  std::memset(&args, 0, sizeof(args));
+  args.x0 = x0;
+  args.x_out = x_out;
+  args.f_out = f_out;
+  args.g_out = g_out;
+  args.progress_out = progress_out;
+  args.obj_params = ctx->params_dev;
+  args.per_problem = desc.per_problem_data;
+  args.per_problem_stride = desc.per_problem_stride;
+  args.B = B;
+  args.n = desc.n;
+  args.m = 1;
+  args.stop = desc.stop;
+  args.hess_from_functor = 1;
+  args.hessian_condition_stop = desc.hessian_condition_stop;
+  rc = setup_trace(ctx, &desc, B, stream, args);
+  if (rc != MI355_OK) return rc;
+  return dispatch_newton_descent(ctx, W, desc.objective, args, dc, stream);
 }

@@ -486,6 +486,60 @@ class BatchedTrustRegionNewton(BatchedLbfgs):
         return x, f, g, prog
 
 
+class BatchedNewtonDescent(BatchedTrustRegionNewton):
+    """Batched `NewtonDescent<F>` (reference solver/newton_descent.h): per step d = (H + safe_guard I).lu().solve(-g) and
+    the Armijo search with the Newton curvature term (linesearch/armijo.h, Armijo<F, 2>) from alpha = 1; n <= 64,
+    objectives whose device functor has a hess_full (Rosenbrock, DiagQuadratic, user functors built with
+    newton_descent=True).
+
+    safe_guard, armijo_c, armijo_rho are the reference's constants (defaults 1e-5, 0.2, 0.9); `condition_hessian` is
+    stopping_progress.condition_hessian (0 = off).  progress.sum_k holds the solve's total trial points.  The search is
+    bounded where the reference's is not: it also ends when alpha * armijo_rho == alpha (include/mi355_lbfgs.h)."""
+    _entry = "mi355_newton_descent_minimize_batch"
+
+    def __init__(self, stopping_progress=None, device=0, context=None, lanes_per_problem=0, condition_hessian=0.0,
+                 **config):
+        BatchedLbfgs.__init__(self, m=1, stopping_progress=stopping_progress, device=device, context=context,
+                              arithmetic="exact", lanes_per_problem=lanes_per_problem,
+                              condition_hessian=condition_hessian)
+        self.config = capi.default_newton_descent_config(**config)
+
+    def minimize(self, objective, x0, want_gradient=True, want_progress=True, per_problem=None, trace=None):
+        torch = self._torch
+        if x0.dtype != torch.float64 or x0.dim() != 2 or not x0.is_cuda:
+            raise ValueError("x0 must be a [B, n] float64 CUDA tensor")
+        self._on_device(x0, "x0")
+        x0 = x0.contiguous()
+        B, n = x0.shape
+        x = torch.empty_like(x0)
+        f = torch.empty(B, dtype=torch.float64, device=x0.device)
+        g = torch.empty_like(x0) if want_gradient else None
+        prog = torch.empty(B * capi.PROGRESS_DTYPE.itemsize, dtype=torch.uint8, device=x0.device) \
+            if want_progress else None
+        d = self._desc(objective, n, *self._pp_device(per_problem, B))
+        if trace is not None:
+            self._trace_keepalive = trace
+            d.trace = trace.c_pointer()
+        capi.check(self.ctx._lib.mi355_newton_descent_minimize_batch(
+            self.ctx.handle, C.byref(d), C.byref(self.config), B, x0.data_ptr(), x.data_ptr(), f.data_ptr(),
+            g.data_ptr() if g is not None else None, prog.data_ptr() if prog is not None else None, self._stream()))
+        return x, f, g, prog
+
+    def minimize_host(self, objective, x0, per_problem=None):
+        """Same through the host-pointer entry point (numpy in, numpy out, synchronous)."""
+        if per_problem is not None:
+            raise ValueError("per-problem data: use minimize() with device tensors")
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        B, n = x0.shape
+        x, g, f = np.empty_like(x0), np.empty_like(x0), np.empty(B)
+        prog = np.zeros(B, dtype=capi.PROGRESS_DTYPE)
+        d = self._desc(objective, n)
+        capi.check(self.ctx._lib.mi355_newton_descent_minimize_batch_host(
+            self.ctx.handle, C.byref(d), C.byref(self.config), B, x0.ctypes.data, x.ctypes.data, f.ctypes.data,
+            g.ctypes.data, prog.ctypes.data))
+        return x, f, g, prog
+
+
 class BatchedNelderMead(BatchedLbfgs):
     """Batched `NelderMead<F>` (reference solver/nelder_mead.h): the derivative-free simplex method, one problem per
     wavefront segment with the simplex and its vertex values in LDS; n <= 64, Rosenbrock, DiagQuadratic and user functors

@@ -1,12 +1,13 @@
-// quartic.hpp — a USER functor with a device Hessian, for TrustRegionNewton (worked example).
+// quartic.hpp — a USER functor with a device Hessian, for TrustRegionNewton and NewtonDescent (worked example).
 //
 // The reference's trust_region_newton_test.cc minimises the 1-D double well f(x) = (x^2 - 2)^2 from a start next to its
 // local maximum at 0.  On the device the function is a functor with the interface of
 // cppnumericalsolvers_amd/csrc/objectives.hpp plus hess_full (H n x n, column major, in the segment's LDS); a build of the
-// library compiles it into the trust-region kernels only:
+// library compiles it into the trust-region and Newton-descent kernels only:
 //     _build.build(output=".../libmi355_lbfgs_tr.so",
 //                  user_objectives=[dict(name="quartic", header=<this file>, type="user_examples::QuarticDoubleWell",
-//                                        id=100, lbfgs=False, lbfgsb=False, trust_region=True)])
+//                                        id=100, lbfgs=False, lbfgsb=False, trust_region=True, newton_descent=True)])
+// In more than one dimension the function still reads x_0 alone (g and H are zero elsewhere).
 // Operation order: t = x x - 2, f = t t, g = (4 x) t, H = (12 x) x - 8 (tests/trust_region/tr_twin.hpp states the same).
 #pragma once
 
@@ -27,9 +28,10 @@ struct QuarticDoubleWell {
     return t * t;
   }
   template <int W, int E>
-  __device__ __forceinline__ void hess_full(const double (&x)[E], double* Hm, int, int sl) const {
+  __device__ __forceinline__ void hess_full(const double (&x)[E], double* Hm, int n, int sl) const {
     const double x0 = mi355::seg_coordinate<W, E>(x, 0, sl);
-    if (sl == 0) Hm[0] = (12.0 * x0) * x0 - 8.0;
+    // (n > 1: the function reads x_0 alone, every other entry of H is zero)
+    for (int t = sl; t < n * n; t += W) Hm[t] = (t == 0) ? (12.0 * x0) * x0 - 8.0 : 0.0;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
   }

@@ -455,6 +455,52 @@ int mi355_nelder_mead_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfg
                                           double* x_out, double* f_out, double* g_out,
                                           mi355_lbfgs_progress* progress_out);
 
+/* ---- NewtonDescent --------------------------------------------------------
+ * The constants of cppoptlib::solver::NewtonDescent (solver/newton_descent.h:69) and of its line search
+ * Armijo<F, 2> (linesearch/armijo.h:85-86; constexpr there, fields here).  mi355_newton_descent_default_config() fills
+ * the defaults. */
+typedef struct mi355_newton_descent_config {
+  double safe_guard; /* 1e-5: added to the diagonal of H(x) before the LU */
+  double armijo_c;   /* 0.2: c of the sufficient-decrease test f(x + a d) <= f(x) + a (c g.d + (0.5 c) c d'Hd) */
+  double armijo_rho; /* 0.9: alpha shrinks by this factor per rejected trial */
+} mi355_newton_descent_config;
+int mi355_newton_descent_default_config(mi355_newton_descent_config* out);
+
+/* Newton descent: replaces cppoptlib::solver::NewtonDescent<FunctionType>::Minimize (newton_descent.h under
+ * Solver::Minimize, solver/solver.h:181-224) for B problems at once, one problem per segment of a wavefront.  Per step:
+ * H(x) n x n in LDS from the device functor's hess_full, d = (H + safe_guard I).lu().solve(-g) (PartialPivLU: right-looking,
+ * first-maximum pivot, the column-oriented substitutions), the Armijo search of armijo.h:82-102 from alpha = 1 with the
+ * Newton curvature term, x + alpha d; then the stopping tests of Progress::Update (desc->stop), including
+ * condition_hessian (desc->hessian_condition_stop > 0).  Where H(x) is indefinite d may be an ascent direction: the
+ * search then shrinks alpha until x + alpha d rounds to x, the step does not move and the x_delta test ends the solve,
+ * as in the reference.
+ * THE ONE DEPARTURE from the reference: the search is bounded.  alpha *= armijo_rho reaches a fixed point in the
+ * denormals (after 7,050 multiplications by 0.9); where the Armijo condition still fails there the reference never
+ * returns.  The device's trial loop also ends when alpha * armijo_rho == alpha and the step proceeds with that alpha.
+ * Objectives whose device functor has a hess_full: Rosenbrock, DiagQuadratic, and user functors built with
+ * newton_descent=True; n <= 64; exact arithmetic only (MI355_ARITH_FMA is refused).  Everything else returns
+ * MI355_ERR_UNSUPPORTED with the reason.  desc->m, linesearch, history_placement and hessian_from_functor are ignored;
+ * hessian_diagonal must be NULL.  Mapping: lanes_per_problem 0 = the library's choice (the padded width of n, at least
+ * 8; 64 lanes for 16 < n <= 32, measured faster) or 8, 16, 32, 64 >= n; elems_per_lane 0 or 1.  Results do not depend
+ * on the mapping.  config NULL = the defaults.
+ * The fields of mi355_lbfgs_progress for this solver:
+ *   num_iterations  steps (Progress::num_iterations)
+ *   nfev            the objective calls the reference makes, the Hessian-only call of Progress::Update not counted:
+ *                   1 at the start, then per step 1 for g and H, 1 for the search's evaluation at x, 1 per trial point
+ *                   and 1 for the state of the returned point (the kernel evaluates the trial points only)
+ *   sum_k           the total number of trial points of the solve
+ *   x_delta, f_delta, gradient_norm: as for the other solvers (a stalled step gives x_delta = 0). */
+int mi355_newton_descent_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
+                                        const mi355_newton_descent_config* config, int64_t B, const double* x0,
+                                        double* x_out, double* f_out, double* g_out,
+                                        mi355_lbfgs_progress* progress_out, void* stream);
+/* The same with host arrays (g_out and progress_out may be NULL): pinned staging and chunks, as the other _host entry
+ * points; returns when the results are in the host arrays. */
+int mi355_newton_descent_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
+                                             const mi355_newton_descent_config* config, int64_t B, const double* x0,
+                                             double* x_out, double* f_out, double* g_out,
+                                             mi355_lbfgs_progress* progress_out);
+
 /* Duration in ms of the most recent solve kernel on this context, measured with
  * HIP events recorded on the launch stream; blocks until that kernel finished. */
 int mi355_lbfgs_last_kernel_ms(mi355_lbfgs_ctx* ctx, float* ms);

@@ -1,0 +1,43 @@
+// common.h — the C interface shared by the CPU twin (nd_twin.cpp) and the reference harness (ref_harness.cpp): one
+// batched NewtonDescent solve on a built-in objective, the stopping fields of mi355_lbfgs_stop and the config of
+// mi355_newton_descent_config, flattened.
+#pragma once
+#include <cstdint>
+
+extern "C" {
+struct nd_stop {  // = mi355_lbfgs_stop
+  uint64_t num_iterations;
+  double x_delta;
+  int32_t x_delta_violations;
+  double f_delta;
+  int32_t f_delta_violations;
+  int32_t f_delta_relative;
+  double gradient_norm;
+  int32_t gradient_norm_relative;
+  int32_t past;
+  double past_delta;
+};
+struct nd_config {  // = mi355_newton_descent_config (the reference's constexpr constants)
+  double safe_guard, armijo_c, armijo_rho;
+};
+struct nd_progress {  // = mi355_lbfgs_progress
+  int32_t status;
+  uint32_t num_iterations;
+  uint32_t nfev;
+  uint32_t sum_k;
+  double x_delta;
+  double f_delta;
+  double gradient_norm;
+};
+// what the twin saw on the way, per solve (the golden generator's assertions; not part of the device's output)
+struct nd_counters {
+  uint32_t interchanges;      // row interchanges of all the LUs of the solve
+  uint32_t max_trials;        // the longest search, in trial points
+  uint32_t alpha_one_steps;   // steps that accepted alpha = 1
+  uint32_t alpha_less_steps;  // steps that accepted alpha < 1
+  uint32_t fixed_point;       // searches that ended because alpha * rho == alpha (the bounded search)
+};
+}
+
+// objective ids (= mi355_objective, plus the quartic double well of the user-objective example, which reads x_0 alone)
+enum { kNdRosenbrock = 0, kNdDiagQuadratic = 1, kNdQuartic = 100 };
