@@ -107,6 +107,17 @@ class NewtonDescentConfig(C.Structure):
     _fields_ = [("safe_guard", C.c_double), ("armijo_c", C.c_double), ("armijo_rho", C.c_double)]
 
 
+# ... and the first-order solvers' (checked by tests/test_first_order_twin.py)
+FIRST_ORDER_SYMBOLS = ["mi355_armijo_default_config", "mi355_gradient_descent_minimize_batch",
+                       "mi355_gradient_descent_minimize_batch_host", "mi355_conjugated_gradient_descent_minimize_batch",
+                       "mi355_conjugated_gradient_descent_minimize_batch_host"]
+
+
+class ArmijoConfig(C.Structure):
+    """mi355_armijo_config: the constants of the reference's Armijo<F, 1> search (ConjugatedGradientDescent)."""
+    _fields_ = [("c", C.c_double), ("rho", C.c_double), ("alpha_min", C.c_double)]
+
+
 class Desc(C.Structure):
     """mi355_lbfgs_desc."""
     _fields_ = [
@@ -257,6 +268,13 @@ def _bind(L):
                                                       vp, vp, vp, vp, vp, vp]
     L.mi355_newton_descent_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), C.POINTER(NewtonDescentConfig),
                                                            C.c_int64, vp, vp, vp, vp, vp]
+    L.mi355_armijo_default_config.argtypes = [C.POINTER(ArmijoConfig)]
+    L.mi355_gradient_descent_minimize_batch.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.mi355_gradient_descent_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp]
+    L.mi355_conjugated_gradient_descent_minimize_batch.argtypes = [vp, C.POINTER(Desc), C.POINTER(ArmijoConfig),
+                                                                   C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.mi355_conjugated_gradient_descent_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), C.POINTER(ArmijoConfig),
+                                                                        C.c_int64, vp, vp, vp, vp, vp]
     L.mi355_lbfgsb_minimize_batch.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mi355_lbfgsb_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, vp, vp, vp, vp, vp]
     L.mi355_lbfgs_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -344,6 +362,17 @@ def default_newton_descent_config(**overrides):
     for k, v in overrides.items():
         if not hasattr(c, k):
             raise TypeError("NewtonDescent config has no field %r" % k)
+        setattr(c, k, v)
+    return c
+
+
+def default_armijo_config(**overrides):
+    """mi355_armijo_default_config(), with the named fields replaced."""
+    c = ArmijoConfig()
+    check(load().mi355_armijo_default_config(C.byref(c)))
+    for k, v in overrides.items():
+        if not hasattr(c, k):
+            raise TypeError("Armijo config has no field %r" % k)
         setattr(c, k, v)
     return c
 

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/mi355_lbfgs.h"
+#include "first_order_config.hpp"
 #include "lbfgs_kernel.hpp"
 #include "lbfgsb_kernel.hpp"
 #include "nelder_mead_config.hpp"
@@ -81,6 +82,7 @@ struct mi355_lbfgs_ctx {
   int debug_waves = 0;
   long long debug_blocks = 0;
   int debug_general_kernel = 0;  // MI355_DEBUG_GENERAL_KERNEL: never pick the lean solve kernels (A/B runs on one library)
+  int debug_cg_eval_trials = 0;  // MI355_DEBUG_CG_EVAL_TRIALS: ConjugatedGradientDescent runs eval, not value(), at its trial points
 };
 
 namespace mi355 {
@@ -242,6 +244,19 @@ struct UserNewtonDescentRegistration {
   UserNewtonDescentRegistration(int objective_id, UserNewtonDescentFn fn) {
     register_user_newton_descent(objective_id, fn);
   }
+};
+
+// GradientDescent / ConjugatedGradientDescent (dispatch_first_order.hip, first_order_kernel.hpp): method = a
+// FirstOrderMethod, W lanes per problem, E coordinates per lane
+int dispatch_first_order(mi355_lbfgs_ctx* ctx, int method, int W, int E, int objective, const SolveArgs& args,
+                         const FirstOrderDeviceConfig& cfg, hipStream_t stream);
+// ... on a user functor: registered by the unit _build.py generates for first_order=True
+using UserFirstOrderFn = int (*)(mi355_lbfgs_ctx* ctx, int method, int W, int E, const SolveArgs& args,
+                                 const FirstOrderDeviceConfig& cfg, hipStream_t stream);
+void register_user_first_order(int objective_id, UserFirstOrderFn fn);
+UserFirstOrderFn user_first_order(int objective_id);
+struct UserFirstOrderRegistration {
+  UserFirstOrderRegistration(int objective_id, UserFirstOrderFn fn) { register_user_first_order(objective_id, fn); }
 };
 
 // desc->trace (device array pointers) -> the trace fields of SolveArgs; uploads the problem list, zeroes `written`

@@ -990,3 +990,44 @@ extern "C" int mi355_newton_descent_minimize_batch_host(mi355_lbfgs_ctx* ctx, co
                           return mi355_newton_descent_minimize_batch(ctx, dd, config, bc, a, b, f, gg, p, st);
                         });
 }
+
+extern "C" int mi355_gradient_descent_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B,
+                                                          const double* x0, double* x_out, double* f_out, double* g_out,
+                                                          mi355_lbfgs_progress* progress_out) {
+  if (!ctx || !desc) return fail(MI355_ERR_INVALID_ARGUMENT, "null context / desc");
+  if (B < 0) return fail(MI355_ERR_INVALID_ARGUMENT, "negative batch size");
+  if (B == 0)
+    return mi355_gradient_descent_minimize_batch(ctx, desc, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
+  if (desc->n > MI355_LBFGS_MAX_N)   // (the device entry point words the refusal)
+    return mi355_gradient_descent_minimize_batch(ctx, desc, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (desc->n < 1) return fail(MI355_ERR_INVALID_ARGUMENT, "n out of range [1, MI355_LBFGS_MAX_N]");
+  MI355_ENTER_DEVICE(ctx);
+  return run_host_batch(ctx, desc, B, x0, x_out, f_out, g_out, progress_out,
+                        [&](const mi355_lbfgs_desc* dd, int64_t bc, const double* a, double* b, double* f, double* gg,
+                            mi355_lbfgs_progress* p, hipStream_t st) {
+                          return mi355_gradient_descent_minimize_batch(ctx, dd, bc, a, b, f, gg, p, st);
+                        });
+}
+
+extern "C" int mi355_conjugated_gradient_descent_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
+                                                                     const mi355_armijo_config* config, int64_t B,
+                                                                     const double* x0, double* x_out, double* f_out,
+                                                                     double* g_out, mi355_lbfgs_progress* progress_out) {
+  if (!ctx || !desc) return fail(MI355_ERR_INVALID_ARGUMENT, "null context / desc");
+  if (B < 0) return fail(MI355_ERR_INVALID_ARGUMENT, "negative batch size");
+  if (B == 0)
+    return mi355_conjugated_gradient_descent_minimize_batch(ctx, desc, config, 0, nullptr, nullptr, nullptr, nullptr,
+                                                            nullptr, nullptr);
+  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
+  if (desc->n > MI355_LBFGS_MAX_N)   // (the device entry point words the refusal)
+    return mi355_conjugated_gradient_descent_minimize_batch(ctx, desc, config, 0, nullptr, nullptr, nullptr, nullptr,
+                                                            nullptr, nullptr);
+  if (desc->n < 1) return fail(MI355_ERR_INVALID_ARGUMENT, "n out of range [1, MI355_LBFGS_MAX_N]");
+  MI355_ENTER_DEVICE(ctx);
+  return run_host_batch(ctx, desc, B, x0, x_out, f_out, g_out, progress_out,
+                        [&](const mi355_lbfgs_desc* dd, int64_t bc, const double* a, double* b, double* f, double* gg,
+                            mi355_lbfgs_progress* p, hipStream_t st) {
+                          return mi355_conjugated_gradient_descent_minimize_batch(ctx, dd, config, bc, a, b, f, gg, p, st);
+                        });
+}

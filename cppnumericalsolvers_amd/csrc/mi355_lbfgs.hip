@@ -31,6 +31,7 @@ struct UserEntry {
   UserTrustRegionFn trust_region = nullptr;
   UserNelderMeadFn nelder_mead = nullptr;
   UserNewtonDescentFn newton_descent = nullptr;
+  UserFirstOrderFn first_order = nullptr;
   std::string name;
 };
 std::vector<std::pair<int, UserEntry>>& user_table() {
@@ -113,6 +114,23 @@ void register_user_newton_descent(int objective_id, UserNewtonDescentFn fn) {
 UserNewtonDescentFn user_newton_descent(int objective_id) {
   for (auto& e : user_table())
     if (e.first == objective_id) return e.second.newton_descent;
+  return nullptr;
+}
+void register_user_first_order(int objective_id, UserFirstOrderFn fn) {
+  if (objective_id < MI355_OBJ_USER_FIRST) return;
+  for (auto& e : user_table()) {
+    if (e.first == objective_id) {
+      e.second.first_order = fn;
+      return;
+    }
+  }
+  UserEntry u;
+  u.first_order = fn;
+  user_table().emplace_back(objective_id, u);
+}
+UserFirstOrderFn user_first_order(int objective_id) {
+  for (auto& e : user_table())
+    if (e.first == objective_id) return e.second.first_order;
   return nullptr;
 }
 static const UserEntry* find_user_objective(int objective_id) {
@@ -512,6 +530,10 @@ int mi355_lbfgs_create(int device, mi355_lbfgs_ctx** out) {
   if (ctx->debug_general_kernel)
     std::fprintf(stderr, "mi355_lbfgs: EXPERIMENT knob active on this context (MI355_DEBUG_GENERAL_KERNEL): the lean solve "
                          "kernels are never picked; results are unchanged\n");
+  if (const char* dbg = std::getenv("MI355_DEBUG_CG_EVAL_TRIALS")) ctx->debug_cg_eval_trials = std::atoi(dbg);
+  if (ctx->debug_cg_eval_trials)
+    std::fprintf(stderr, "mi355_lbfgs: EXPERIMENT knob active on this context (MI355_DEBUG_CG_EVAL_TRIALS): the Armijo trials of "
+                         "ConjugatedGradientDescent run eval instead of value(); results are unchanged\n");
   *out = ctx;
   return MI355_OK;
 }
@@ -1508,4 +1530,124 @@ extern "C" int mi355_newton_descent_minimize_batch(mi355_lbfgs_ctx* ctx, const m
   rc = setup_trace(ctx, &desc, B, stream, args);
   if (rc != MI355_OK) return rc;
   return dispatch_newton_descent(ctx, W, desc.objective, args, dc, stream);
+}
+
+// ---- GradientDescent / ConjugatedGradientDescent (first_order_kernel.hpp) -------------------------------------------
+extern "C" int mi355_armijo_default_config(mi355_armijo_config* out) {
+  if (!out) return fail(MI355_ERR_INVALID_ARGUMENT, "null config");
+  out->c = 0.2;            // linesearch/armijo.h:49-50
+  out->rho = 0.9;
+  out->alpha_min = 1e-8;   // :56
+  return MI355_OK;
+}
+
+namespace {
+int first_order_minimize_batch(const char* solver, int method, mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc_in,
+                               const mi355_armijo_config* config, int64_t B, const double* x0, double* x_out,
+                               double* f_out, double* g_out, mi355_lbfgs_progress* progress_out, void* stream_) {
+  if (!desc_in) return fail(MI355_ERR_INVALID_ARGUMENT, "null desc");
+  // m, the line search field and the Hessian fields mean nothing to these solvers
+  mi355_lbfgs_desc desc = *desc_in;
+  desc.m = 1;
+  desc.linesearch = MI355_LS_MORE_THUENTE;
+  desc.history_placement = 0;
+  desc.hessian_from_functor = 0;
+  desc.hessian_diagonal = nullptr;
+  static thread_local std::string msg;
+  if (desc.hessian_condition_stop != 0.0) {
+    msg = std::string(solver) + ": the condition_hessian test is not evaluated (hessian_condition_stop must be 0)";
+    return fail(MI355_ERR_INVALID_ARGUMENT, msg.c_str());
+  }
+  if (desc.n > MI355_LBFGS_MAX_N) {
+    msg = std::string(solver) + " is built for n <= 256 (x, g and d in registers, up to four coordinates per lane)";
+    return fail(MI355_ERR_UNSUPPORTED, msg.c_str());
+  }
+  int rc = validate(ctx, &desc, B);
+  if (rc != MI355_OK) return rc;
+  if (desc.arithmetic == MI355_ARITH_FMA) {
+    msg = std::string(solver) + " is built for the exact arithmetic only (no MI355_ARITH_FMA)";
+    return fail(MI355_ERR_UNSUPPORTED, msg.c_str());
+  }
+  if (desc.objective != MI355_OBJ_ROSENBROCK && desc.objective != MI355_OBJ_DIAG_QUADRATIC &&
+      !(desc.objective >= MI355_OBJ_USER_FIRST && user_first_order(desc.objective) != nullptr)) {
+    msg = std::string(solver) +
+          (desc.objective >= MI355_OBJ_USER_FIRST
+               ? ": this library holds no first-order kernel for this user objective (build it with first_order=True)"
+               : " is built for objectives without LDS data: Rosenbrock, DiagQuadratic and user functors built with "
+                 "first_order=True; not the ridge forms or the augmented-Lagrangian composite");
+    return fail(MI355_ERR_UNSUPPORTED, msg.c_str());
+  }
+  // the mapping: the padded width at one coordinate per lane up to 64, then 64 lanes at two and four
+  int W = desc.lanes_per_problem, E = desc.elems_per_lane;
+  if (W == 0) {
+    if (E != 0) {
+      msg = std::string(solver) + ": elems_per_lane needs an explicit lanes_per_problem";
+      return fail(MI355_ERR_INVALID_ARGUMENT, msg.c_str());
+    }
+    W = 8;
+    while (W < desc.n && W < 64) W <<= 1;
+  } else if (!(W == 8 || W == 16 || W == 32 || W == 64)) {
+    msg = std::string(solver) + ": lanes_per_problem must be 0, 8, 16, 32 or 64";
+    return fail(MI355_ERR_INVALID_ARGUMENT, msg.c_str());
+  }
+  if (E == 0) E = (desc.n <= W) ? 1 : ((desc.n <= 2 * W) ? 2 : 4);
+  if (!(E == 1 || ((E == 2 || E == 4) && W == 64)) || W * E < desc.n) {
+    msg = std::string(solver) +
+          ": the mapping must cover n with 8, 16, 32 or 64 lanes at one coordinate per lane, or 64 lanes at two or four";
+    return fail(MI355_ERR_INVALID_ARGUMENT, msg.c_str());
+  }
+  mi355_armijo_config c;
+  mi355_armijo_default_config(&c);
+  if (config) c = *config;
+  // (the search must end: alpha shrinks towards alpha_min)
+  if (!(c.rho > 0.0 && c.rho < 1.0) || !(c.alpha_min > 0.0)) {
+    msg = std::string(solver) + ": the Armijo config needs 0 < rho < 1 and alpha_min > 0";
+    return fail(MI355_ERR_INVALID_ARGUMENT, msg.c_str());
+  }
+  FirstOrderDeviceConfig dc;
+  dc.armijo_c = c.c;
+  dc.armijo_rho = c.rho;
+  dc.armijo_alpha_min = c.alpha_min;
+  // measurement switch (scripts/first_order_bench.py): 1 = the Armijo trials run eval instead of value()
+  dc.eval_trials = ctx->debug_cg_eval_trials ? 1 : 0;
+  if (B == 0) return MI355_OK;
+  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MI355_ENTER_DEVICE(ctx);
+  rc = upload_params(ctx, &desc, W, E, stream);
+  if (rc != MI355_OK) return rc;
+  SolveArgs args;
+  std::memset(&args, 0, sizeof(args));
+  args.x0 = x0;
+  args.x_out = x_out;
+  args.f_out = f_out;
+  args.g_out = g_out;
+  args.progress_out = progress_out;
+  args.obj_params = ctx->params_dev;
+  args.per_problem = desc.per_problem_data;
+  args.per_problem_stride = desc.per_problem_stride;
+  args.B = B;
+  args.n = desc.n;
+  args.m = 1;
+  args.stop = desc.stop;
+  rc = setup_trace(ctx, &desc, B, stream, args);
+  if (rc != MI355_OK) return rc;
+  return dispatch_first_order(ctx, method, W, E, desc.objective, args, dc, stream);
+}
+}  // namespace
+
+extern "C" int mi355_gradient_descent_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B,
+                                                     const double* x0, double* x_out, double* f_out, double* g_out,
+                                                     mi355_lbfgs_progress* progress_out, void* stream) {
+  return first_order_minimize_batch("GradientDescent", kGradientDescent, ctx, desc, nullptr, B, x0, x_out, f_out, g_out,
+                                    progress_out, stream);
+}
+
+extern "C" int mi355_conjugated_gradient_descent_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
+                                                                const mi355_armijo_config* config, int64_t B,
+                                                                const double* x0, double* x_out, double* f_out,
+                                                                double* g_out, mi355_lbfgs_progress* progress_out,
+                                                                void* stream) {
+  return first_order_minimize_batch("ConjugatedGradientDescent", kConjugatedGradientDescent, ctx, desc, config, B, x0,
+                                    x_out, f_out, g_out, progress_out, stream);
 }

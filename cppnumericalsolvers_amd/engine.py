@@ -540,6 +540,84 @@ class BatchedNewtonDescent(BatchedTrustRegionNewton):
         return x, f, g, prog
 
 
+class BatchedGradientDescent(BatchedLbfgs):
+    """Batched `GradientDescent<F>` (reference solver/gradient_descent.h with the More-Thuente search): per step the search
+    runs along -g from alpha = 1 and the step is x - rate g; n <= 256, x and g in registers; Rosenbrock, DiagQuadratic
+    and user functors built with first_order=True.  progress.sum_k holds the solve's total trial points."""
+    _entry = "mi355_gradient_descent_minimize_batch"
+    _config = None
+
+    def __init__(self, stopping_progress=None, device=0, context=None, lanes_per_problem=0, elems_per_lane=0):
+        super().__init__(m=1, stopping_progress=stopping_progress, device=device, context=context, arithmetic="exact",
+                         lanes_per_problem=lanes_per_problem, elems_per_lane=elems_per_lane)
+
+    def _desc(self, objective, n, per_problem=None, per_problem_stride=0):
+        d = super()._desc(objective, n, per_problem, per_problem_stride)
+        d.hessian_from_functor = 0     # (first-order solvers: no Hessian field is read)
+        d.hessian_diagonal = None
+        d.hessian_condition = 0.0
+        d.hessian_condition_stop = 0.0
+        return d
+
+    def _config_args(self):
+        return () if self._config is None else (C.byref(self._config),)
+
+    def minimize(self, objective, x0, want_gradient=True, want_progress=True, per_problem=None, trace=None):
+        torch = self._torch
+        if x0.dtype != torch.float64 or x0.dim() != 2 or not x0.is_cuda:
+            raise ValueError("x0 must be a [B, n] float64 CUDA tensor")
+        self._on_device(x0, "x0")
+        x0 = x0.contiguous()
+        B, n = x0.shape
+        x = torch.empty_like(x0)
+        f = torch.empty(B, dtype=torch.float64, device=x0.device)
+        g = torch.empty_like(x0) if want_gradient else None
+        prog = torch.empty(B * capi.PROGRESS_DTYPE.itemsize, dtype=torch.uint8, device=x0.device) \
+            if want_progress else None
+        d = self._desc(objective, n, *self._pp_device(per_problem, B))
+        if trace is not None:
+            self._trace_keepalive = trace
+            d.trace = trace.c_pointer()
+        capi.check(getattr(self.ctx._lib, self._entry)(
+            self.ctx.handle, C.byref(d), *self._config_args(), B, x0.data_ptr(), x.data_ptr(), f.data_ptr(),
+            g.data_ptr() if g is not None else None, prog.data_ptr() if prog is not None else None, self._stream()))
+        return x, f, g, prog
+
+    def minimize_host(self, objective, x0, per_problem=None):
+        """Same through the host-pointer entry point (numpy in, numpy out, synchronous)."""
+        if per_problem is not None:
+            raise ValueError("per-problem data: use minimize() with device tensors")
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        B, n = x0.shape
+        x, g, f = np.empty_like(x0), np.empty_like(x0), np.empty(B)
+        prog = np.zeros(B, dtype=capi.PROGRESS_DTYPE)
+        d = self._desc(objective, n)
+        capi.check(getattr(self.ctx._lib, self._entry + "_host")(
+            self.ctx.handle, C.byref(d), *self._config_args(), B, x0.ctypes.data, x.ctypes.data, f.ctypes.data,
+            g.ctypes.data, prog.ctypes.data))
+        return x, f, g, prog
+
+
+class BatchedConjugatedGradientDescent(BatchedGradientDescent):
+    """Batched `ConjugatedGradientDescent<F>` (reference solver/conjugated_gradient_descent.h): d = -g at the first step,
+    then the Fletcher-Reeves beta = (g.g) / (g_prev.g_prev) and d = -g + beta d, with the backtracking search
+    Armijo<F, 1> (linesearch/armijo.h) from alpha = 1; the same objectives and sizes as BatchedGradientDescent.
+
+    armijo_c, armijo_rho, armijo_alpha_min are the reference's constants (defaults 0.2, 0.9, 1e-8)."""
+    _entry = "mi355_conjugated_gradient_descent_minimize_batch"
+
+    def __init__(self, stopping_progress=None, device=0, context=None, lanes_per_problem=0, elems_per_lane=0,
+                 armijo_c=None, armijo_rho=None, armijo_alpha_min=None):
+        super().__init__(stopping_progress=stopping_progress, device=device, context=context,
+                         lanes_per_problem=lanes_per_problem, elems_per_lane=elems_per_lane)
+        given = dict(c=armijo_c, rho=armijo_rho, alpha_min=armijo_alpha_min)
+        self._config = capi.default_armijo_config(**{k: float(v) for k, v in given.items() if v is not None})
+
+    @property
+    def config(self):
+        return self._config
+
+
 class BatchedNelderMead(BatchedLbfgs):
     """Batched `NelderMead<F>` (reference solver/nelder_mead.h): the derivative-free simplex method, one problem per
     wavefront segment with the simplex and its vertex values in LDS; n <= 64, Rosenbrock, DiagQuadratic and user functors

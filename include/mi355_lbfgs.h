@@ -501,6 +501,64 @@ int mi355_newton_descent_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_l
                                              double* x_out, double* f_out, double* g_out,
                                              mi355_lbfgs_progress* progress_out);
 
+/* ---- GradientDescent and ConjugatedGradientDescent -----------------------------
+ * The constants of the backtracking search Armijo<F, 1> (linesearch/armijo.h:49-50, :56; constexpr there, fields
+ * here) that ConjugatedGradientDescent uses.  mi355_armijo_default_config() fills the defaults. */
+typedef struct mi355_armijo_config {
+  double c;         /* 0.2: the sufficient-decrease test is f(x + a d) <= f(x) + a (c g.d) */
+  double rho;       /* 0.9: alpha shrinks by this factor per rejected trial; 0 < rho < 1 */
+  double alpha_min; /* 1e-8: the search also ends when alpha <= alpha_min; > 0 */
+} mi355_armijo_config;
+int mi355_armijo_default_config(mi355_armijo_config* out);
+
+/* Gradient descent: replaces cppoptlib::solver::GradientDescent<FunctionType, MoreThuente>::Minimize
+ * (solver/gradient_descent.h:64-73 under Solver::Minimize, solver/solver.h:181-224) for B problems at once, one problem
+ * per segment of a wavefront, x and g in registers.  Per step the More-Thuente search of the scalar overload
+ * (linesearch/more_thuente.h:63-77, cvsrch :137-256) runs along -g from alpha = 1 and the step returns x - rate g, the
+ * bits of the search's last trial point; then the stopping tests of Progress::Update (desc->stop).  Where cvsrch
+ * refuses (g.g >= 0 fails to be negative: it underflowed to 0) the reference still steps by rate = 1, and so does the
+ * kernel.
+ * Objectives: Rosenbrock, DiagQuadratic, and user functors built with first_order=True; n <= 256; exact arithmetic only
+ * (MI355_ARITH_FMA is refused).  Everything else returns MI355_ERR_UNSUPPORTED with the reason.  desc->m, linesearch,
+ * history_placement and the Hessian fields are ignored; hessian_condition_stop must be 0.  Mapping: lanes_per_problem
+ * 0 = the library's choice (the padded width of n from 8 to 64 lanes at one coordinate per lane, 64 lanes at two
+ * coordinates per lane for 64 < n <= 128 and at four above), or 8, 16, 32, 64 with elems_per_lane 0 (= the smallest
+ * that covers n), 1, or — at 64 lanes — 2 or 4.  Results do not depend on the mapping.
+ * The fields of mi355_lbfgs_progress for this solver:
+ *   num_iterations  steps (Progress::num_iterations)
+ *   nfev            the objective calls the reference makes: 1 at the start, then per step 1 in OptimizationStep, 1 for
+ *                   the search's evaluation at x, 1 per trial point and 1 for the state of the returned point (the
+ *                   kernel evaluates the trial points, and the returned point only after a refused search)
+ *   sum_k           the total number of trial points of the solve
+ *   x_delta, f_delta, gradient_norm: as for the other solvers.
+ * A NaN in x_out, f_out, g_out or these three doubles is written as the quiet NaN 0x7ff8000000000000 whatever its sign
+ * and payload were (they are the processor's, not the reference's); this holds for conjugated gradient descent too. */
+int mi355_gradient_descent_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B,
+                                          const double* x0, double* x_out, double* f_out, double* g_out,
+                                          mi355_lbfgs_progress* progress_out, void* stream);
+/* The same with host arrays (g_out and progress_out may be NULL): pinned staging and chunks, as the other _host entry
+ * points; returns when the results are in the host arrays. */
+int mi355_gradient_descent_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B,
+                                               const double* x0, double* x_out, double* f_out, double* g_out,
+                                               mi355_lbfgs_progress* progress_out);
+
+/* Conjugated gradient descent: replaces cppoptlib::solver::ConjugatedGradientDescent<FunctionType>::Minimize
+ * (InitializeSolver solver/conjugated_gradient_descent.h:62-65, OptimizationStep :67-85, under Solver::Minimize) the
+ * same way.  Per step d = -g at the first iteration, else beta = (g.g) / (g_prev.g_prev) and d = -g + beta d (a zero
+ * denominator gives inf or NaN, as in the reference); the backtracking search Armijo<F, 1> (linesearch/armijo.h:45-64)
+ * from alpha = 1: while f(x + alpha d) > f(x) + alpha c (g.d) and alpha > alpha_min, alpha *= rho; then x + alpha d.
+ * The trial points are evaluated through the functor's value() where it has one, and one full evaluation follows at
+ * the accepted point.  Objectives, n, arithmetic, mapping, ignored fields and refusals as for gradient descent.
+ * config NULL = the defaults.  nfev counts 1 more at the start (InitializeSolver); per step as above. */
+int mi355_conjugated_gradient_descent_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
+                                                     const mi355_armijo_config* config, int64_t B, const double* x0,
+                                                     double* x_out, double* f_out, double* g_out,
+                                                     mi355_lbfgs_progress* progress_out, void* stream);
+int mi355_conjugated_gradient_descent_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
+                                                          const mi355_armijo_config* config, int64_t B,
+                                                          const double* x0, double* x_out, double* f_out, double* g_out,
+                                                          mi355_lbfgs_progress* progress_out);
+
 /* Duration in ms of the most recent solve kernel on this context, measured with
  * HIP events recorded on the launch stream; blocks until that kernel finished. */
 int mi355_lbfgs_last_kernel_ms(mi355_lbfgs_ctx* ctx, float* ms);
