@@ -13,7 +13,7 @@ REPO = os.path.dirname(HERE)
 REFERENCE = "/root/reference"
 TWIN_LIB = os.path.join(ND_DIR, "_build", "libnd_twin.so")
 
-ROSENBROCK, DIAG_QUADRATIC, QUARTIC = 0, 1, 100
+ROSENBROCK, DIAG_QUADRATIC, QUARTIC, DENSE = 0, 1, 100, 101
 REF_ORDER, DEVICE_ORDER = 0, 1
 
 STOP_DTYPE = np.dtype([("num_iterations", "<u8"), ("x_delta", "<f8"), ("x_delta_violations", "<i4"), ("f_delta", "<f8"),
@@ -24,7 +24,10 @@ CONFIG_DTYPE = np.dtype([(f, "<f8") for f in CONFIG_FIELDS], align=True)
 PROGRESS_DTYPE = np.dtype([("status", "<i4"), ("num_iterations", "<u4"), ("nfev", "<u4"), ("sum_k", "<u4"),
                            ("x_delta", "<f8"), ("f_delta", "<f8"), ("gradient_norm", "<f8")], align=True)
 COUNTERS_DTYPE = np.dtype([("interchanges", "<u4"), ("max_trials", "<u4"), ("alpha_one_steps", "<u4"),
-                           ("alpha_less_steps", "<u4"), ("fixed_point", "<u4")], align=True)
+                           ("alpha_less_steps", "<u4"), ("fixed_point", "<u4"), ("pivot_ties", "<u4"),
+                           ("zero_columns", "<u4"), ("conditions", "<u4"), ("pivot_distance", "<u4", (64,)),
+                           ("min_condition_margin", "<f8")], align=True)
+NO_MUTATION, TRANSPOSE_BEFORE_LU, CHAIN_WALKS_ROW = 0, 1, 2    # nd_twin::Mutation
 DEFAULT_CONFIG = dict(safe_guard=1e-5, armijo_c=0.2, armijo_rho=0.9)   # newton_descent.h:69, armijo.h:85-86
 # the stopping presets: DefaultStoppingSolverProgress (progress.h; as mi355_lbfgs_default_stop fills it) and the
 # package's parity preset (cppnumericalsolvers_amd.parity_stop)
@@ -90,6 +93,13 @@ def _twin_lib():
     if _twin is None:
         _twin = C.CDLL(TWIN_LIB)
         _declare(_twin.nd_twin_solve, 2, 1)
+        _declare(_twin.nd_twin_solve_mutated, 3, 0)
+        _twin.nd_twin_lu_factor.restype = C.c_int
+        _twin.nd_twin_lu_factor.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        _twin.nd_twin_lu_solve.restype = C.c_int
+        _twin.nd_twin_lu_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        _twin.nd_twin_condition.restype = C.c_double
+        _twin.nd_twin_condition.argtypes = [C.c_void_p, C.c_int]
         _twin.nd_twin_search.restype = C.c_int
         _twin.nd_twin_search.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
     return _twin
@@ -105,6 +115,46 @@ def twin_solve(objective, x0, params=None, stop=None, config=None, condition_sto
                  config if config is not None else make_config(), condition_stop,
                  (order, W if W is not None else padded_width(n)), counters=True)
     return out if counters else out[:4]
+
+
+def twin_solve_mutated(mutation, objective, x0, params=None, stop=None, config=None, condition_stop=0.0, order=REF_ORDER,
+                       W=None):
+    """twin_solve with one of the twin's deliberate bugs planted (TRANSPOSE_BEFORE_LU, CHAIN_WALKS_ROW)."""
+    n = np.asarray(x0).shape[1]
+    return _solve(_twin_lib().nd_twin_solve_mutated, objective, x0, params,
+                  stop if stop is not None else make_stop(**STOP_PRESETS["default"]),
+                  config if config is not None else make_config(), condition_stop,
+                  (order, W if W is not None else padded_width(n), mutation))
+
+
+def _column_major(A):
+    A = np.asarray(A, dtype=np.float64)
+    assert A.ndim == 2 and A.shape[0] == A.shape[1]
+    return np.ascontiguousarray(A.T).reshape(-1).copy()
+
+
+def twin_lu(A):
+    """The twin's LU of A ([n, n], A[i, j] = A(i, j)): (LU [n, n] with the unit-lower multipliers below the diagonal,
+    piv: row piv[k] was exchanged with row k at step k)."""
+    n = A.shape[0]
+    a, piv = _column_major(A), np.zeros(n, dtype=np.int32)
+    assert _twin_lib().nd_twin_lu_factor(a.ctypes.data, piv.ctypes.data, n) == 0
+    return a.reshape(n, n).T.copy(), piv
+
+
+def twin_lu_solve(LU, piv, b):
+    """x of A x = b through the twin's substitutions on the factors of twin_lu."""
+    n = LU.shape[0]
+    a, x = _column_major(LU), np.array(b, dtype=np.float64)
+    piv = np.ascontiguousarray(piv, dtype=np.int32)
+    assert _twin_lib().nd_twin_lu_solve(a.ctypes.data, piv.ctypes.data, x.ctypes.data, n) == 0
+    return x
+
+
+def twin_condition(A):
+    """The twin's ||A||_F ||A^-1||_F."""
+    a = _column_major(A)
+    return _twin_lib().nd_twin_condition(a.ctypes.data, A.shape[0])
 
 
 def twin_search(objective, x, d, params=None, config=None, order=REF_ORDER, W=None):

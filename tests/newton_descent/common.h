@@ -36,8 +36,15 @@ struct nd_counters {
   uint32_t alpha_one_steps;   // steps that accepted alpha = 1
   uint32_t alpha_less_steps;  // steps that accepted alpha < 1
   uint32_t fixed_point;       // searches that ended because alpha * rho == alpha (the bounded search)
+  uint32_t pivot_ties;        // LU columns whose non-zero maximum was attained more than once (the first one is the pivot)
+  uint32_t zero_columns;      // LU columns with best == 0 (no interchange, no division; the solve divides by that zero)
+  uint32_t conditions;        // condition numbers the stopping test evaluated
+  uint32_t pivot_distance[64];  // histogram of p - k over every column of the steps' LUs
+  double min_condition_margin;  // the smallest |condition - threshold| / threshold of those (+inf: none evaluated)
 };
 }
+enum { kNdMaxN = 64 };
 
-// objective ids (= mi355_objective, plus the quartic double well of the user-objective example, which reads x_0 alone)
-enum { kNdRosenbrock = 0, kNdDiagQuadratic = 1, kNdQuartic = 100 };
+// objective ids (= mi355_objective, plus the quartic double well of the user-objective example, which reads x_0 alone,
+// and the dense quartic of examples/user_objective_dense: params = S (n x n, column major), b (n), kappa)
+enum { kNdRosenbrock = 0, kNdDiagQuadratic = 1, kNdQuartic = 100, kNdDense = 101 };

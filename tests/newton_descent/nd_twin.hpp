@@ -8,6 +8,9 @@
 // The LU, the solve and the chains v_j = sum_i (k d_i) H(i, j) contain no reduction over lanes and are the same in both
 // orders.  The search is bounded as the kernel's is (it also ends when alpha * rho == alpha); the counters tell which
 // solves got there, and those are not comparable with the reference, which would not have returned.
+// kNdDense (examples/user_objective_dense/dense_quartic.hpp) is the one objective with a dense, possibly asymmetric
+// Hessian; `Mutation` plants the transposition bugs a symmetric Hessian hides, so that a test can show the recorded inputs
+// tell them apart.
 // Built with -ffp-contract=off.
 #pragma once
 #include <algorithm>
@@ -21,6 +24,8 @@
 namespace nd_twin {
 
 enum Order { kRefOrder = 0, kDeviceOrder = 1 };
+// deliberate bugs (tests only): H(j, i) handed to the LU for H(i, j); the chain of the search walking row j for column j
+enum Mutation { kNoMutation = 0, kTransposeBeforeLu = 1, kChainWalksRow = 2 };
 
 inline double tree_sum(const double* v, int len) {  // pairwise tree over a power-of-two length
   if (len == 1) return v[0];
@@ -81,6 +86,25 @@ struct Objective {
       }
       return o.sum(term) + params[n];
     }
+    if (id == kNdDense) {
+      // S x row by row, ascending in j with the first term a product; x_j reaches the other lanes of the device through a
+      // butterfly over zeros (seg_coordinate): x_j + 0.0
+      const double *S = params, *b = params + n * n, kappa = params[n * n + n];
+      std::vector<double> lin(L, 0.0), quart(L, 0.0);
+      for (int i = 0; i < n; ++i) {
+        double s = 0.0;
+        for (int j = 0; j < n; ++j) {
+          const double xj = (o.order == kDeviceOrder) ? x[j] + 0.0 : x[j];
+          s = (j == 0) ? S[i] * xj : s + S[j * n + i] * xj;
+        }
+        const double q = x[i] * x[i];
+        g[i] = (s - b[i]) + kappa * (q * x[i]);
+        term[i] = x[i] * s;
+        lin[i] = b[i] * x[i];
+        quart[i] = q * q;
+      }
+      return (0.5 * o.sum(term) - o.sum(lin)) + (0.25 * kappa) * o.sum(quart);
+    }
     const double t = x[0] * x[0] - 2.0;  // kNdQuartic
     g[0] = (4.0 * x[0]) * t;
     return t * t;
@@ -89,6 +113,12 @@ struct Objective {
     H.assign(static_cast<size_t>(n) * n, 0.0);
     if (id == kNdQuartic) {
       H[0] = (12.0 * x[0]) * x[0] - 8.0;
+      return;
+    }
+    if (id == kNdDense) {  // H(i, j) = S(i, j) as given (column major, never symmetrised), the diagonal + (3 kappa) x_i^2
+      const double kappa = params[n * n + n];
+      for (int t = 0; t < n * n; ++t) H[t] = params[t];
+      for (int i = 0; i < n; ++i) H[i * n + i] = params[i * n + i] + (3.0 * kappa) * (x[i] * x[i]);
       return;
     }
     for (int j = 0; j < n; ++j) {
@@ -104,8 +134,15 @@ struct Objective {
   }
 };
 
+// what the pivot searches of an LU met (the golden generators' assertions)
+struct LuStats {
+  uint32_t distance[kNdMaxN];  // histogram of p - k over the columns
+  uint32_t ties;               // columns whose non-zero maximum was attained more than once (the first one is taken)
+  uint32_t zero_columns;       // columns with best == 0: no interchange, no division
+};
+
 // PartialPivLU in the pinned order (oracle/eigen_shim/Eigen/LU, csrc/lu_device.hpp); returns the row interchanges made
-inline uint32_t lu_factor(std::vector<double>& A, std::vector<int>& piv, int n) {
+inline uint32_t lu_factor(std::vector<double>& A, std::vector<int>& piv, int n, LuStats* stats = nullptr) {
   uint32_t interchanges = 0;
   piv.assign(n, 0);
   for (int k = 0; k < n; ++k) {
@@ -114,6 +151,13 @@ inline uint32_t lu_factor(std::vector<double>& A, std::vector<int>& piv, int n) 
     for (int i = k + 1; i < n; ++i)
       if (std::fabs(A[k * n + i]) > best) best = std::fabs(A[k * n + i]), p = i;
     piv[k] = p;
+    if (stats != nullptr) {
+      int attained = 0;
+      for (int i = k; i < n; ++i) attained += std::fabs(A[k * n + i]) == best;
+      if (best != 0.0 && attained > 1) ++stats->ties;
+      if (best == 0.0) ++stats->zero_columns;
+      if (p - k < kNdMaxN) ++stats->distance[p - k];
+    }
     if (best != 0.0) {
       if (p != k) {
         ++interchanges;
@@ -162,7 +206,7 @@ struct SearchResult {
 // gradient in xt, gt
 inline SearchResult armijo(const Objective& obj, const Ops& o, const nd_config& c, const std::vector<double>& x, double f,
                            const std::vector<double>& g, const std::vector<double>& H, const std::vector<double>& d,
-                           std::vector<double>& xt, std::vector<double>& gt) {
+                           std::vector<double>& xt, std::vector<double>& gt, Mutation mutation = kNoMutation) {
   const int n = obj.n, L = o.L;
   double alpha = 1.0;
   xt.assign(L, 0.0);
@@ -173,8 +217,8 @@ inline SearchResult armijo(const Objective& obj, const Ops& o, const nd_config& 
   std::vector<double> kd(L), v(L, 0.0);
   for (int j = 0; j < L; ++j) kd[j] = kq * d[j];
   for (int j = 0; j < n; ++j) {
-    double s = kd[0] * H[j * n];
-    for (int i = 1; i < n; ++i) s = s + kd[i] * H[j * n + i];
+    double s = kd[0] * (mutation == kChainWalksRow ? H[j] : H[j * n]);
+    for (int i = 1; i < n; ++i) s = s + kd[i] * (mutation == kChainWalksRow ? H[i * n + j] : H[j * n + i]);
     v[j] = s;
   }
   const double cache = c.armijo_c * gd + o.dot(v, d);
@@ -205,7 +249,8 @@ struct Trajectory {
 
 inline void solve_one(const Objective& obj, Order order, int W, const nd_stop& st, double condition_stop,
                       const nd_config& c, const double* x0, double* x_out, double* f_out, double* g_out,
-                      nd_progress* prog, nd_counters* counters, Trajectory* traj = nullptr) {
+                      nd_progress* prog, nd_counters* counters, Trajectory* traj = nullptr,
+                      Mutation mutation = kNoMutation) {
   const int n = obj.n;
   const Ops o{order, n, order == kDeviceOrder ? W : n};
   const int L = o.L;
@@ -214,7 +259,9 @@ inline void solve_one(const Objective& obj, Order order, int W, const nd_stop& s
   for (int j = 0; j < n; ++j) x[j] = x0[j];
   double f = obj.eval(o, x, g);
   uint32_t nfev = 1, trials_total = 0, it = 0;
-  nd_counters cnt{0, 0, 0, 0, 0};
+  nd_counters cnt{};
+  cnt.min_condition_margin = std::numeric_limits<double>::infinity();
+  LuStats lus{};
   obj.hessian(x, H);
   int xv = 0, fv = 0, status = kContinue;
   double x_delta = 0, f_delta = 0, gnorm = 0;
@@ -226,14 +273,19 @@ inline void solve_one(const Objective& obj, Order order, int W, const nd_stop& s
     A.resize(H.size());
     for (size_t t = 0; t < H.size(); ++t) A[t] = H[t] + 0.0;   // + safe_guard * Identity, element by element
     for (int j = 0; j < n; ++j) A[j * n + j] = H[j * n + j] + c.safe_guard;
-    cnt.interchanges += lu_factor(A, piv, n);
+    if (mutation == kTransposeBeforeLu) {
+      const std::vector<double> At = A;
+      for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) A[j * n + i] = At[i * n + j];
+    }
+    cnt.interchanges += lu_factor(A, piv, n, &lus);
     for (int j = 0; j < L; ++j) d[j] = -g[j];
     lu_solve(A, piv, d.data(), n);
     for (int j = n; j < L; ++j) d[j] = 0.0;
     nfev += 1;  // Armijo's function(x, &gradient, &hessian)
     const double fprev = f;
     const std::vector<double> xprev = x;
-    const SearchResult r = armijo(obj, o, c, x, f, g, H, d, xt, gt);
+    const SearchResult r = armijo(obj, o, c, x, f, g, H, d, xt, gt, mutation);
     nfev += r.trials + 1;  // the trials, and the state rebuild of Solver::Minimize
     trials_total += r.trials;
     cnt.max_trials = std::max(cnt.max_trials, r.trials);
@@ -276,7 +328,12 @@ inline void solve_one(const Objective& obj, Order order, int W, const nd_stop& s
     }
     if (!decided) {
       obj.hessian(x, H);
-      if (condition_stop > 0 && condition(H, n) > condition_stop) status = kCondition;
+      if (condition_stop > 0) {
+        const double cond = condition(H, n);
+        ++cnt.conditions;
+        cnt.min_condition_margin = std::min(cnt.min_condition_margin, std::fabs(cond - condition_stop) / condition_stop);
+        if (cond > condition_stop) status = kCondition;
+      }
     }
     if (traj != nullptr && traj->count < traj->capacity) {
       double* row = traj->rows + 6 * traj->count;
@@ -297,6 +354,9 @@ inline void solve_one(const Objective& obj, Order order, int W, const nd_stop& s
   prog->x_delta = x_delta;
   prog->f_delta = f_delta;
   prog->gradient_norm = gnorm;
+  cnt.pivot_ties = lus.ties;
+  cnt.zero_columns = lus.zero_columns;
+  for (int t = 0; t < kNdMaxN; ++t) cnt.pivot_distance[t] = lus.distance[t];
   if (counters) *counters = cnt;
 }
 

@@ -1,9 +1,9 @@
 // ref_harness.cpp — the reference's NewtonDescent (solver/newton_descent.h and linesearch/armijo.h of the reference
 // tree, unmodified) over the Eigen stand-in of oracle/eigen_shim, behind the C interface of common.h.  Compiled at test
 // time (or by tests/golden/make_golden_nd.py) into a directory outside the repository; nothing built from it is kept in
-// the tree.  The functors restate the device functors' formulas (csrc/objectives.hpp, examples/user_objective_quartic)
-// with the reference's sequential sums and count every call, so that the twin in reference order can match them bit for
-// bit, nfev included.  Dynamic dimension, as the reference's own test pair uses it (src/test/verify.cc): a state built
+// the tree.  The functors restate the device functors' formulas (csrc/objectives.hpp, examples/user_objective_quartic,
+// examples/user_objective_dense) with the reference's sequential sums and count every call, so that the twin in
+// reference order can match them bit for bit, nfev included.  Dynamic dimension, as the reference's own test pair uses it (src/test/verify.cc): a state built
 // from x alone then has an empty gradient and Solver::Minimize rebuilds it (solver.h:210-216), the one evaluation per
 // step the kernel counts.  The reference's constants (safe_guard, c, rho) are constexpr: the config is not read.
 #include <cstdint>
@@ -103,6 +103,39 @@ class Quartic : public FunctionCRTP<Quartic, double, DifferentiabilityMode::Seco
   }
 };
 
+// the dense quartic of examples/user_objective_dense: f = 0.5 x . (S x) - b . x + (kappa / 4) sum x_i^4 with S column
+// major and used as given (H(i, j) = S(i, j), not symmetrised); row i of S x ascending in j, first term a product;
+// q_i = x_i x_i, g_i = (sx_i - b_i) + kappa (q_i x_i), H(i, i) = S(i, i) + (3 kappa) q_i;
+// f = (0.5 sum x_i sx_i - sum b_i x_i) + (0.25 kappa) sum q_i q_i, each sum ascending
+class Dense : public FunctionCRTP<Dense, double, DifferentiabilityMode::Second>, public Counter {
+ public:
+  const double* params = nullptr;
+  ScalarType operator()(const VectorType& x, VectorType* gradient = nullptr, MatrixType* hessian = nullptr) const {
+    count(gradient, hessian);
+    const int n = static_cast<int>(x.size());
+    const double *S = params, *b = params + n * n, kappa = params[n * n + n];
+    double quad = 0.0, lin = 0.0, quart = 0.0;
+    if (gradient) *gradient = VectorType::Zero(n);
+    for (int i = 0; i < n; ++i) {
+      double s = S[i] * x[0];
+      for (int j = 1; j < n; ++j) s = s + S[j * n + i] * x[j];
+      const double q = x[i] * x[i];
+      if (gradient) (*gradient)[i] = (s - b[i]) + kappa * (q * x[i]);
+      const double t0 = x[i] * s, t1 = b[i] * x[i], t2 = q * q;
+      quad = (i == 0) ? t0 : quad + t0;
+      lin = (i == 0) ? t1 : lin + t1;
+      quart = (i == 0) ? t2 : quart + t2;
+    }
+    if (hessian) {
+      *hessian = MatrixType::Zero(n, n);
+      for (int j = 0; j < n; ++j)
+        for (int i = 0; i < n; ++i) (*hessian)(i, j) = S[j * n + i];
+      for (int i = 0; i < n; ++i) (*hessian)(i, i) = S[i * n + i] + (3.0 * kappa) * (x[i] * x[i]);
+    }
+    return (0.5 * quad - lin) + (0.25 * kappa) * quart;
+  }
+};
+
 // where the reference's step callback records the per-iteration states of problem 0 (null = no recording): one row
 // (num_iterations, status, value, x_delta, f_delta, gradient_norm) and the iterate per Progress::Update, in order
 struct TrajectorySink {
@@ -177,6 +210,10 @@ extern "C" int nd_ref_solve(int objective, int n, int64_t B, const double* param
     solve(fn, n, B, st, condition_stop, x0, x_out, f_out, g_out, prog);
   } else if (objective == kNdQuartic) {
     Quartic fn;
+    solve(fn, n, B, st, condition_stop, x0, x_out, f_out, g_out, prog);
+  } else if (objective == kNdDense) {
+    Dense fn;
+    fn.params = params;
     solve(fn, n, B, st, condition_stop, x0, x_out, f_out, g_out, prog);
   } else {
     return -1;

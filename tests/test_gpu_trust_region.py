@@ -1,11 +1,13 @@
 """TrustRegionNewton on the MI355X (csrc/trust_region_kernel.hpp): bit for bit the CPU twin in device order on every
 recorded case and under two lane mappings, within 1e-6 of the reference's recorded solves with the same status, the
-Python driver equal to the host entry point, and clean refusals."""
+Python driver equal to the host entry point, the dense-Hessian user functor (asymmetric and indefinite Hessians, the
+condition test at n up to 64), and clean refusals."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import dense_cases as D
 import tr_cases
 import tr_lib as T
 
@@ -21,7 +23,22 @@ def _objective(amd, case):
     if obj == T.DIAG_QUADRATIC:
         n = case["x0"].shape[1]
         return amd.DiagQuadratic(case["params"][:n], float(case["params"][n]))
+    if obj == T.DENSE:
+        return amd.Objective(101, case["params"], "dense_quartic")
     return None
+
+
+_user_ctx = []
+
+
+def _context(case):
+    """The default library's shared context, or — the dense quartic is a user functor — one on libmi355_lbfgs_tr.so."""
+    import cppnumericalsolvers_amd as amd
+    if int(case["objective"]) != T.DENSE:
+        return None
+    if not _user_ctx:
+        _user_ctx.append(amd.Context(0, library=_library("libmi355_lbfgs_tr.so")))
+    return _user_ctx[0]
 
 
 def _stop(capi, rec):
@@ -35,13 +52,14 @@ def _config(rec):
     return {k: rec[k][0].item() for k in T.CONFIG_FIELDS}
 
 
-def _device_solve(case, lanes=0):
+def _device_solve(case, lanes=0, trace=None):
     import torch
     import cppnumericalsolvers_amd as amd
     from cppnumericalsolvers_amd import capi
     solver = amd.BatchedTrustRegionNewton(stopping_progress=_stop(capi, case["stop"]), lanes_per_problem=lanes,
-                                          condition_hessian=float(case["condition_stop"]), **_config(case["config"]))
-    x, f, g, p = solver.minimize(_objective(amd, case), torch.from_numpy(case["x0"]).to("cuda:0"))
+                                          condition_hessian=float(case["condition_stop"]), context=_context(case),
+                                          **_config(case["config"]))
+    x, f, g, p = solver.minimize(_objective(amd, case), torch.from_numpy(case["x0"]).to("cuda:0"), trace=trace)
     torch.cuda.synchronize()
     return x.cpu().numpy(), f.cpu().numpy(), g.cpu().numpy(), amd.progress_to_numpy(p)
 
@@ -71,6 +89,12 @@ def test_device_matches_twin_and_reference(case):
     # on the loose-preset Rosenbrock rows, where both runs must have converged (status 3 or 4) and x* must lie within 1e-3
     # (twice the largest shift the data shows), so that a gross regression still fails there.
     rp = case["progress"]
+    if "x" not in case:
+        # a dense case above n = 33 keeps a digest of the reference's x*: the twin in reference order, checked against the
+        # digest, stands in for it
+        case = {**case, "x": D.reference_x(case, T.twin_solve(int(case["objective"]), case["x0"], case["params"],
+                                                              case["stop"], case["config"],
+                                                              float(case["condition_stop"]))[0])}
     done = rp["status"] != 1     # (an unbounded problem stopped by the iteration limit has no x* to compare)
     # (an overflowing start stays at f = inf in both: equal infinities compare equal here)
     np.testing.assert_allclose(f[done], case["f"][done], rtol=0, atol=1e-6, err_msg=case["name"])
@@ -83,13 +107,18 @@ def test_device_matches_twin_and_reference(case):
         np.testing.assert_allclose(x[done], case["x"][done], rtol=0, atol=1e-6, err_msg=case["name"])
 
 
-@pytest.mark.parametrize("name", ["rosenbrock_n7_default", "rosenbrock_n32_parity", "edge_condition_hessian"])
+@pytest.mark.parametrize("name", ["rosenbrock_n7_default", "rosenbrock_n32_parity", "edge_condition_hessian",
+                                  "dense_spd_n09_default", "dense_spd_n33_default"])
 def test_lane_mappings_same_bits(name):
+    """(The dense case at n = 9 also runs at its padded width of 16 lanes; at n = 33 the padded width is 64.)"""
     case = next(c for c in CASES if c["name"] == name)
     a = _device_solve(case)
     b = _device_solve(case, lanes=64)
     for u, v in zip(a, b):
         assert u.tobytes() == v.tobytes(), name
+    if name == "dense_spd_n09_default":
+        for u, v in zip(a, _device_solve(case, lanes=16)):
+            assert u.tobytes() == v.tobytes(), name + " (16 lanes)"
 
 
 def test_python_driver_equals_host_entry():
@@ -192,6 +221,8 @@ def test_trajectory_matches_reference_callback(case):
     trace = amd.Trace([0], capacity=1024, n=n, device=torch.device("cuda", 0), with_x=True)
     if int(case["objective"]) == T.QUARTIC:
         _quartic_solve(case, trace=trace)
+    elif int(case["objective"]) == T.DENSE:
+        _device_solve(case, trace=trace)
     else:
         solver = amd.BatchedTrustRegionNewton(stopping_progress=_stop(capi, case["stop"]),
                                               condition_hessian=float(case["condition_stop"]), **_config(case["config"]))

@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+import dense_cases as D
 import nd_cases
 import nd_lib as T
 
@@ -34,6 +35,11 @@ def _twin(case, order, **kw):
 def test_twin_reference_order_matches_golden(case):
     twin = _twin(case, T.REF_ORDER, counters=True)
     assert (twin[4]["fixed_point"] == 0).all()    # (a solve that got there is not comparable with the reference)
+    if "g" not in case:
+        # a dense case: g* (and x* above n = 33) recorded as digests of the reference's bytes (dense_cases.py)
+        assert D.same_as_recorded(case, "x", twin[0]), case["name"] + ": x"
+        assert D.same_as_recorded(case, "g", twin[2]), case["name"] + ": g"
+        case = {**case, "x": twin[0], "g": twin[2]}
     assert_same((case["x"], case["f"], case["g"], case["progress"]), twin, case["name"])
 
 
@@ -55,6 +61,79 @@ def test_golden_covers_the_paths():
     marked = [c["name"] for c in CASES if int(c["marked"])]
     assert len(marked) <= nd_cases.MAX_MARKED_FRACTION * len(CASES)
     assert not [m for m in marked if m.startswith(nd_cases.NEVER_MARKED)]
+
+
+def test_dense_cases_reach_the_lu_and_the_condition_test():
+    """What the generator asserted of the dense-Hessian cases, from the twin's counters today: far pivots at n >= 33 (past
+    the 8-wide chunks of the device's search and past 32 rows), pivots beyond the neighbouring row on both sides of the
+    n = 8 boundary, exact ties, both step kinds, condition numbers away from the threshold with both decisions taken, and
+    an all-zero pivot column in the device-only edge case."""
+    by = {c["name"]: c for c in CASES}
+    cnt = {nm: _twin(c, T.REF_ORDER, counters=True)[4] for nm, c in by.items() if nm.startswith("dense_")}
+    assert sorted(int(nm[11:13]) for nm in cnt if nm.startswith("dense_spd_") and nm.endswith("_default")) == list(D.DIMS)
+    for n in D.DIMS:
+        for kind in ("dense_spd_n%02d_default", "dense_spd_n%02d_parity", "dense_asym_n%02d_default"):
+            assert by[kind % n]["x0"].shape == (8, n)
+        h = cnt["dense_spd_n%02d_default" % n]["pivot_distance"].sum(axis=0)
+        if n >= 33:
+            assert h[8:].sum() >= 100 and h[32:].sum() >= 10, (n, h[8:].sum(), h[32:].sum())
+        if n in (8, 9):
+            assert h[2:].sum() >= 10, (n, h[2:].sum())
+    assert any(cnt["dense_spd_n%02d_default" % n]["pivot_ties"].sum() >= 1 for n in D.DIMS if n >= 9)
+    assert sum(int(v["alpha_one_steps"].sum()) for v in cnt.values()) >= 1
+    assert sum(int(v["alpha_less_steps"].sum()) for v in cnt.values()) >= 1
+    for n in (9, 33, 64):
+        name = "dense_condition_n%02d" % n
+        status = by[name]["progress"]["status"]
+        margin = min(cnt[name]["min_condition_margin"].min(),
+                     _twin(by[name], T.DEVICE_ORDER, counters=True)[4]["min_condition_margin"].min())
+        assert margin >= 1e-9, name      # (every condition number either order evaluates)
+        assert (status == 5).any() and (status != 5).any(), (name, status)
+        assert (by[name]["progress"]["num_iterations"][status == 5] >= 2).any(), name
+    z = D.zero_column_case()
+    zc = T.twin_solve(D.DENSE, z["x0"], z["params"], z["stop"], z["config"], 0.0, counters=True)[4]
+    assert (zc["zero_columns"] >= 1).all() and (zc["fixed_point"] == 0).all()
+
+
+ASYMMETRIC_CASES = [c for c in CASES if c["name"].startswith("dense_asym_")]
+
+
+@pytest.mark.parametrize("case", ASYMMETRIC_CASES, ids=[c["name"] for c in ASYMMETRIC_CASES])
+def test_asymmetric_cases_notice_a_transposed_hessian(case):
+    """H(i, j) != H(j, i) in the last bits: the twin with H transposed before the LU gives other bytes on at least one
+    row, in both orders, so the device-equals-twin comparison on this case would catch that read in the kernel.  (The
+    chain of the search: test_strongly_asymmetric_cases_notice_a_chain_walking_a_row.)"""
+    H = D.hessian(case["params"], case["x0"][0])
+    assert H.tobytes() != np.ascontiguousarray(H.T).tobytes()
+    assert D.nd_transposition_shows(case)
+
+
+@pytest.mark.parametrize("n", sorted(D.CHAIN_CASES))
+def test_strongly_asymmetric_cases_notice_a_chain_walking_a_row(n):
+    """dense_cases.chain_case: S with an antisymmetric part of 2^60 and more.  The twin whose search walks row j of H for
+    column j in v_j = sum_i (k d_i) H(i, j) gives other bytes on at least one row, in both orders, so the
+    device-equals-twin comparison on this case (tests/test_gpu_newton_descent.py) holds the kernel's column walk to
+    its comment: it does not rely on a symmetric H."""
+    case = D.chain_case(n)
+    assert D.nd_mutation_shows(T.CHAIN_WALKS_ROW, case)
+    out = _twin(case, T.DEVICE_ORDER, counters=True)
+    assert np.isfinite(out[0]).all() and (out[4]["alpha_less_steps"] >= 1).any()
+
+
+def test_dense_kappa0_lands_on_the_linear_solve():
+    """kappa = 0: H = S is constant and every step is a full Newton step on (S + 1e-5 I), which leaves 1e-5 / lambda_min
+    of the error behind; under the parity stop three of them end the solve.  x* against S x = b solved with 50 digits,
+    to 1e-6."""
+    import mpmath
+    case = next(c for c in CASES if c["name"] == "dense_kappa0_n17")
+    n = case["x0"].shape[1]
+    p = case["params"]
+    assert p[n * n + n] == 0.0 and (case["progress"]["num_iterations"] <= 3).all()
+    assert (_twin(case, T.REF_ORDER, counters=True)[4]["alpha_less_steps"] == 0).all()
+    with mpmath.workdps(50):
+        S = mpmath.matrix(p[:n * n].reshape(n, n).T.tolist())
+        exact = np.array([float(v) for v in mpmath.lu_solve(S, mpmath.matrix(p[n * n:n * n + n].tolist()))])
+    np.testing.assert_allclose(case["x"], np.tile(exact, (case["x0"].shape[0], 1)), rtol=0, atol=1e-6)
 
 
 TRAJECTORY_CASES = [c for c in CASES if "trajectory" in c]

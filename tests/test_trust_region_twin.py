@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+import dense_cases as D
 import tr_cases
 import tr_lib as T
 
@@ -28,6 +29,11 @@ def assert_same(ref, twin, what):
 def test_twin_reference_order_matches_golden(case):
     twin = T.twin_solve(int(case["objective"]), case["x0"], case["params"], case["stop"], case["config"],
                         float(case["condition_stop"]), order=T.REF_ORDER)
+    if "g" not in case:
+        # a dense case: g* (and x* above n = 33) recorded as digests of the reference's bytes (dense_cases.py)
+        assert D.same_as_recorded(case, "x", twin[0]), case["name"] + ": x"
+        assert D.same_as_recorded(case, "g", twin[2]), case["name"] + ": g"
+        case = {**case, "x": twin[0], "g": twin[2]}
     assert_same((case["x"], case["f"], case["g"], case["progress"]), twin, case["name"])
 
 
@@ -43,6 +49,58 @@ def test_golden_covers_the_quirks():
     p = by["diag_quadratic_indefinite"]["progress"]
     assert (p["status"] == 1).all() and np.isfinite(by["diag_quadratic_indefinite"]["f"]).all()
     assert (by["edge_condition_hessian"]["progress"]["status"] == 5).any()
+
+
+DENSE_CASES = [c for c in CASES if c["name"].startswith("dense_")]
+
+
+def _twin_ex(case, order, **kw):
+    return T.twin_solve_ex(int(case["objective"]), case["x0"], case["params"], case["stop"], case["config"],
+                           float(case["condition_stop"]), order=order, **kw)
+
+
+def test_dense_cases_reach_the_cg_and_the_condition_test():
+    """What the generator asserted of the dense-Hessian cases, from the twin's counters today: CG runs of 3 iterations and
+    more at n >= 33, negative-curvature exits and boundary hits on the indefinite family, at least 4 starts per case, and
+    condition numbers away from the threshold, in both summation orders, with both decisions taken."""
+    by = {c["name"]: c for c in DENSE_CASES}
+    cnt = {nm: _twin_ex(c, T.REF_ORDER)[4] for nm, c in by.items()}
+    for n in D.DIMS:
+        for kind in ("dense_spd_n%02d_default", "dense_spd_n%02d_parity", "dense_asym_n%02d_default",
+                     "dense_indefinite_n%02d_default"):
+            assert 4 <= by[kind % n]["x0"].shape[0] <= 8 and by[kind % n]["x0"].shape[1] == n
+    assert any(cnt["dense_spd_n%02d_default" % n]["max_cg_iterations"].max() >= 3 for n in D.DIMS if n >= 33)
+    assert sum(int(v["negative_curvature_exits"].sum()) for k, v in cnt.items() if k.startswith("dense_indefinite_")) >= 1
+    assert sum(int(v["boundary_hits"].sum()) for k, v in cnt.items() if k.startswith("dense_indefinite_")) >= 1
+    for n in (9, 33, 64):
+        name = "dense_condition_n%02d" % n
+        status = by[name]["progress"]["status"]
+        margin = min(cnt[name]["min_condition_margin"].min(),
+                     _twin_ex(by[name], T.DEVICE_ORDER)[4]["min_condition_margin"].min())
+        assert margin >= 1e-9, name
+        assert (status == 5).any() and (status != 5).any(), (name, status)
+        assert (by[name]["progress"]["num_iterations"][status == 5] >= 2).any(), name
+
+
+@pytest.mark.parametrize("case", DENSE_CASES, ids=[c["name"] for c in DENSE_CASES])
+def test_dense_device_order_within_the_contract(case):
+    """This file marks no case: on every recorded dense row the twin's two summation orders end within 1e-6 in x* and f*
+    with the same status, so the device can be held to the reference's record there."""
+    import nd_cases
+    assert not nd_cases.misses_contract(_twin_ex(case, T.REF_ORDER), _twin_ex(case, T.DEVICE_ORDER)).any()
+
+
+ASYMMETRIC_CASES = [c for c in DENSE_CASES if c["name"].startswith("dense_asym_")]
+
+
+@pytest.mark.parametrize("case", ASYMMETRIC_CASES, ids=[c["name"] for c in ASYMMETRIC_CASES])
+def test_asymmetric_cases_notice_a_transposed_product(case):
+    """H(i, j) != H(j, i) in the last bits: the twin with H d walking a column of H for a row gives other bytes on at
+    least one row, in both orders, so the device-equals-twin comparison on this case would catch that read in the
+    kernel."""
+    H = D.hessian(case["params"], case["x0"][0])
+    assert H.tobytes() != np.ascontiguousarray(H.T).tobytes()
+    assert D.tr_transposition_shows(case)
 
 
 @pytest.mark.skipif(not os.path.isdir(T.REFERENCE), reason="needs the reference tree")

@@ -13,7 +13,7 @@ REPO = os.path.dirname(HERE)
 REFERENCE = "/root/reference"
 TWIN_LIB = os.path.join(TR_DIR, "_build", "libtr_twin.so")
 
-ROSENBROCK, DIAG_QUADRATIC, QUARTIC = 0, 1, 100
+ROSENBROCK, DIAG_QUADRATIC, QUARTIC, DENSE = 0, 1, 100, 101
 REF_ORDER, DEVICE_ORDER = 0, 1
 
 STOP_DTYPE = np.dtype([("num_iterations", "<u8"), ("x_delta", "<f8"), ("x_delta_violations", "<i4"), ("f_delta", "<f8"),
@@ -25,6 +25,10 @@ CONFIG_DTYPE = np.dtype([(f, "<i4" if f in ("cg_max_iterations_floor", "rejectio
                          for f in CONFIG_FIELDS], align=True)
 PROGRESS_DTYPE = np.dtype([("status", "<i4"), ("num_iterations", "<u4"), ("nfev", "<u4"), ("sum_k", "<u4"),
                            ("x_delta", "<f8"), ("f_delta", "<f8"), ("gradient_norm", "<f8")], align=True)
+COUNTERS_DTYPE = np.dtype([("max_cg_iterations", "<u4"), ("subproblems_of_3_cg_iterations", "<u4"),
+                           ("negative_curvature_exits", "<u4"), ("boundary_hits", "<u4"), ("conditions", "<u4"),
+                           ("min_condition_margin", "<f8")], align=True)
+NO_MUTATION, PRODUCT_WALKS_COLUMN = 0, 1    # tr_twin::Mutation
 DEFAULT_CONFIG = dict(initial_radius=1.0, max_radius=1e10, acceptance_threshold=0.15, shrink_factor=0.25,
                       expand_factor=2.0, rho_low=0.25, rho_high=0.75, cg_forcing_coefficient=0.5,
                       cg_max_iterations_floor=10, min_radius=1e-12, rejection_retry_limit=50)
@@ -88,6 +92,37 @@ def twin_solve(objective, x0, params=None, stop=None, config=None, condition_sto
             W *= 2
     return _solve(_twin, objective, x0, params, stop if stop is not None else make_stop(**STOP_PRESETS["default"]),
                   config if config is not None else make_config(), condition_stop, (order, W))
+
+
+_twin_ex = None
+
+
+def twin_solve_ex(objective, x0, params=None, stop=None, config=None, condition_stop=0.0, order=REF_ORDER, W=None,
+                  mutation=NO_MUTATION):
+    """twin_solve with the twin's counters as a fifth result and, mutation = PRODUCT_WALKS_COLUMN, its deliberate bug
+    planted (H d walking a column of H for a row)."""
+    global _twin_ex
+    if _twin_ex is None:
+        _twin_ex = C.CDLL(TWIN_LIB).tr_twin_solve_ex
+        _twin_ex.restype = C.c_int
+        _twin_ex.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p] + \
+                            [C.c_int] * 3 + [C.c_void_p] * 6
+    x0 = np.ascontiguousarray(x0, dtype=np.float64)
+    B, n = x0.shape
+    if W is None:
+        W = 8
+        while W < n:
+            W *= 2
+    stop = stop if stop is not None else make_stop(**STOP_PRESETS["default"])
+    config = config if config is not None else make_config()
+    params = np.ascontiguousarray(params if params is not None else np.zeros(1), dtype=np.float64)
+    x, g, f = np.empty_like(x0), np.empty_like(x0), np.empty(B)
+    prog, cnt = np.zeros(B, dtype=PROGRESS_DTYPE), np.zeros(B, dtype=COUNTERS_DTYPE)
+    rc = _twin_ex(objective, n, B, params.ctypes.data, stop.ctypes.data, C.c_double(condition_stop), config.ctypes.data,
+                  order, W, mutation, x0.ctypes.data, x.ctypes.data, f.ctypes.data, g.ctypes.data, prog.ctypes.data,
+                  cnt.ctypes.data)
+    assert rc == 0, "unsupported solve"
+    return x, f, g, prog, cnt
 
 
 def build_reference(out_dir):

@@ -33,7 +33,17 @@ struct tr_progress {  // = mi355_lbfgs_progress
   double f_delta;
   double gradient_norm;
 };
+// what the twin saw on the way, per solve (the golden generator's assertions; not part of the device's output)
+struct tr_counters {
+  uint32_t max_cg_iterations;               // the longest CG-Steihaug run of a subproblem
+  uint32_t subproblems_of_3_cg_iterations;  // subproblems that ran at least 3 CG iterations
+  uint32_t negative_curvature_exits;        // CG runs that met d'H d <= 0 (or NaN)
+  uint32_t boundary_hits;                   // steps extended to the trust-region boundary (either reason)
+  uint32_t conditions;                      // condition numbers the stopping test evaluated
+  double min_condition_margin;              // the smallest |condition - threshold| / threshold (+inf: none evaluated)
+};
 }
 
-// objective ids (= mi355_objective, plus the 1-D quartic double well of the user-objective example)
-enum { kTrRosenbrock = 0, kTrDiagQuadratic = 1, kTrQuartic = 100 };
+// objective ids (= mi355_objective, plus the 1-D quartic double well of the user-objective example and the dense quartic
+// of examples/user_objective_dense: params = S (n x n, column major), b (n), kappa)
+enum { kTrRosenbrock = 0, kTrDiagQuadratic = 1, kTrQuartic = 100, kTrDense = 101 };

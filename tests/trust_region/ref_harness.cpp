@@ -1,8 +1,9 @@
 // ref_harness.cpp — the reference's TrustRegionNewton (solver/trust_region_newton.h of the reference tree, unmodified)
 // over the Eigen stand-in of oracle/eigen_shim, behind the C interface of common.h.  Compiled at test time (or by
 // tests/golden/make_golden_tr.py) into a directory outside the repository; nothing built from it is kept in the tree.
-// The functors restate the device functors' formulas (csrc/objectives.hpp, examples/user_objective_quartic), with the
-// reference's sequential sums, so that the twin in reference order can match them bit for bit.
+// The functors restate the device functors' formulas (csrc/objectives.hpp, examples/user_objective_quartic,
+// examples/user_objective_dense), with the reference's sequential sums, so that the twin in reference order can match
+// them bit for bit.
 #include <cstdint>
 #include <cstring>
 
@@ -110,6 +111,44 @@ class Quartic : public FunctionCRTP<Quartic, double, DifferentiabilityMode::Seco
   }
 };
 
+// the dense quartic of examples/user_objective_dense: f = 0.5 x . (S x) - b . x + (kappa / 4) sum x_i^4 with S column
+// major and used as given (H(i, j) = S(i, j), not symmetrised); row i of S x ascending in j, first term a product;
+// q_i = x_i x_i, g_i = (sx_i - b_i) + kappa (q_i x_i), H(i, i) = S(i, i) + (3 kappa) q_i;
+// f = (0.5 sum x_i sx_i - sum b_i x_i) + (0.25 kappa) sum q_i q_i, each sum ascending
+template <int N>
+class Dense : public FunctionCRTP<Dense<N>, double, DifferentiabilityMode::Second, N>, public Counter {
+ public:
+  using typename FunctionCRTP<Dense<N>, double, DifferentiabilityMode::Second, N>::ScalarType;
+  using typename FunctionCRTP<Dense<N>, double, DifferentiabilityMode::Second, N>::VectorType;
+  using typename FunctionCRTP<Dense<N>, double, DifferentiabilityMode::Second, N>::MatrixType;
+ public:
+  const double* params = nullptr;
+  ScalarType operator()(const VectorType& x, VectorType* gradient = nullptr, MatrixType* hessian = nullptr) const {
+    count(gradient, hessian);
+    const int n = static_cast<int>(x.size());
+    const double *S = params, *b = params + n * n, kappa = params[n * n + n];
+    double quad = 0.0, lin = 0.0, quart = 0.0;
+    if (gradient) *gradient = VectorType::Zero();
+    for (int i = 0; i < n; ++i) {
+      double s = S[i] * x[0];
+      for (int j = 1; j < n; ++j) s = s + S[j * n + i] * x[j];
+      const double q = x[i] * x[i];
+      if (gradient) (*gradient)[i] = (s - b[i]) + kappa * (q * x[i]);
+      const double t0 = x[i] * s, t1 = b[i] * x[i], t2 = q * q;
+      quad = (i == 0) ? t0 : quad + t0;
+      lin = (i == 0) ? t1 : lin + t1;
+      quart = (i == 0) ? t2 : quart + t2;
+    }
+    if (hessian) {
+      *hessian = MatrixType::Zero();
+      for (int j = 0; j < n; ++j)
+        for (int i = 0; i < n; ++i) (*hessian)(i, j) = S[j * n + i];
+      for (int i = 0; i < n; ++i) (*hessian)(i, i) = S[i * n + i] + (3.0 * kappa) * (x[i] * x[i]);
+    }
+    return (0.5 * quad - lin) + (0.25 * kappa) * quart;
+  }
+};
+
 // where the reference's step callback records the per-iteration states of problem 0 (null = no recording): one row
 // (num_iterations, status, value, x_delta, f_delta, gradient_norm) and the iterate per Progress::Update, in order
 struct TrajectorySink {
@@ -197,6 +236,10 @@ int solve_n(int objective, int64_t B, const double* params, const tr_stop* st, d
     fn.a = params;
     fn.c = params[N];
     solve(fn, N, B, st, condition_stop, cfg, x0, x_out, f_out, g_out, prog);
+  } else if (objective == kTrDense) {
+    Dense<N> fn;
+    fn.params = params;
+    solve(fn, N, B, st, condition_stop, cfg, x0, x_out, f_out, g_out, prog);
   } else if (objective == kTrQuartic && N == 1) {
     Quartic fn;
     solve(fn, 1, B, st, condition_stop, cfg, x0, x_out, f_out, g_out, prog);
@@ -212,7 +255,8 @@ extern "C" int tr_ref_solve(int objective, int n, int64_t B, const double* param
                             double* g_out, tr_progress* prog) {
   switch (n) {
 #define TR_N(N) case N: return solve_n<N>(objective, B, params, st, condition_stop, cfg, x0, x_out, f_out, g_out, prog);
-    TR_N(1) TR_N(2) TR_N(3) TR_N(4) TR_N(5) TR_N(6) TR_N(7) TR_N(8) TR_N(12) TR_N(16) TR_N(32) TR_N(64)
+    TR_N(1) TR_N(2) TR_N(3) TR_N(4) TR_N(5) TR_N(6) TR_N(7) TR_N(8) TR_N(9) TR_N(12) TR_N(16) TR_N(17) TR_N(32)
+    TR_N(33) TR_N(63) TR_N(64)
 #undef TR_N
   }
   return -1;

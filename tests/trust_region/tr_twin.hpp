@@ -5,8 +5,11 @@
 //   kDeviceOrder  they are the pairwise trees over the padded width W of the kernel's segment butterflies
 //                 (csrc/trust_region_kernel.hpp, wave_primitives.hpp seg_sum), every vector carried over the W lanes with
 //                 the padding lanes computed as the kernel computes them: bit for bit the device.
-// H d is the ascending row sum in both (the kernel forms it that way).  Built with -ffp-contract=off.
+// H d is the ascending row sum in both (the kernel forms it that way).  kTrDense
+// (examples/user_objective_dense/dense_quartic.hpp) is the one objective with a dense, possibly asymmetric Hessian;
+// `Mutation` plants the transposed product a symmetric Hessian hides.  Built with -ffp-contract=off.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <limits>
@@ -17,6 +20,8 @@
 namespace tr_twin {
 
 enum Order { kRefOrder = 0, kDeviceOrder = 1 };
+// a deliberate bug (tests only): H d walking column j of H for row j
+enum Mutation { kNoMutation = 0, kProductWalksColumn = 1 };
 
 inline double tree_sum(const double* v, int len) {  // pairwise tree over a power-of-two length
   if (len == 1) return v[0];
@@ -77,12 +82,37 @@ struct Objective {
       }
       return o.sum(term) + params[n];
     }
+    if (id == kTrDense) {
+      // S x row by row, ascending in j with the first term a product; x_j reaches the other lanes of the device through a
+      // butterfly over zeros (seg_coordinate): x_j + 0.0
+      const double *S = params, *b = params + n * n, kappa = params[n * n + n];
+      std::vector<double> lin(L, 0.0), quart(L, 0.0);
+      for (int i = 0; i < n; ++i) {
+        double s = 0.0;
+        for (int j = 0; j < n; ++j) {
+          const double xj = (o.order == kDeviceOrder) ? x[j] + 0.0 : x[j];
+          s = (j == 0) ? S[i] * xj : s + S[j * n + i] * xj;
+        }
+        const double q = x[i] * x[i];
+        g[i] = (s - b[i]) + kappa * (q * x[i]);
+        term[i] = x[i] * s;
+        lin[i] = b[i] * x[i];
+        quart[i] = q * q;
+      }
+      return (0.5 * o.sum(term) - o.sum(lin)) + (0.25 * kappa) * o.sum(quart);
+    }
     const double t = x[0] * x[0] - 2.0;  // kTrQuartic
     g[0] = (4.0 * x[0]) * t;
     return t * t;
   }
   void hessian(const std::vector<double>& x, std::vector<double>& H) const {
     H.assign(static_cast<size_t>(n) * n, 0.0);
+    if (id == kTrDense) {  // H(i, j) = S(i, j) as given (column major, never symmetrised), the diagonal + (3 kappa) x_i^2
+      const double kappa = params[n * n + n];
+      for (int t = 0; t < n * n; ++t) H[t] = params[t];
+      for (int i = 0; i < n; ++i) H[i * n + i] = params[i * n + i] + (3.0 * kappa) * (x[i] * x[i]);
+      return;
+    }
     for (int j = 0; j < n; ++j) {
       if (id == kTrRosenbrock) {
         const bool has_a = j + 1 < n, has_b = j > 0;
@@ -137,8 +167,10 @@ enum { kContinue = 0, kIterationLimit = 1, kXDelta = 2, kFDelta = 3, kGradient =
 
 inline void solve_one(const Objective& obj, Order order, int W, const tr_stop& st, double condition_stop,
                       const tr_config& c, const double* x0, double* x_out, double* f_out, double* g_out,
-                      tr_progress* prog) {
+                      tr_progress* prog, tr_counters* counters = nullptr, Mutation mutation = kNoMutation) {
   const int n = obj.n;
+  tr_counters cnt{};
+  cnt.min_condition_margin = std::numeric_limits<double>::infinity();
   const Ops o{order, n, order == kDeviceOrder ? W : n};
   const int L = o.L;
   std::vector<double> x(L, 0.0), g, gt, xt(L), H;
@@ -146,8 +178,8 @@ inline void solve_one(const Objective& obj, Order order, int W, const tr_stop& s
   auto hess_times = [&](const std::vector<double>& d) {
     std::vector<double> out(L, 0.0);
     for (int j = 0; j < n; ++j) {
-      double s = H[j] * d[0];
-      for (int k = 1; k < n; ++k) s = s + H[j + k * n] * d[k];
+      double s = (mutation == kProductWalksColumn ? H[j * n] : H[j]) * d[0];
+      for (int k = 1; k < n; ++k) s = s + (mutation == kProductWalksColumn ? H[j * n + k] : H[j + k * n]) * d[k];
       out[j] = s;
     }
     return out;
@@ -184,13 +216,14 @@ inline void solve_one(const Objective& obj, Order order, int W, const tr_stop& s
         const double tau = (-b + std::sqrt(std::max(disc, 0.0))) / (2.0 * a);
         for (int j = 0; j < L; ++j) p[j] = p[j] + tau * d[j];
         hit = true;
+        ++cnt.boundary_hits;
       };
       if (!(std::sqrt(rr) <= tol)) {
         for (int k = 0; k < cg_max; ++k) {
           ++cgi;
           const std::vector<double> hd = hess_times(d);
           const double curv = o.dot(d, hd);
-          if (!(curv > 0.0)) { to_boundary(); break; }
+          if (!(curv > 0.0)) { ++cnt.negative_curvature_exits; to_boundary(); break; }
           const double alpha = rr / curv;
           std::vector<double> pc(L);
           for (int j = 0; j < L; ++j) pc[j] = p[j] + alpha * d[j];
@@ -215,6 +248,8 @@ inline void solve_one(const Objective& obj, Order order, int W, const tr_stop& s
       if (rho < c.rho_low) radius *= c.shrink_factor;
       else if (rho > c.rho_high && hit) radius = std::min(c.expand_factor * radius, c.max_radius);
       cg_total += cgi;
+      cnt.max_cg_iterations = std::max(cnt.max_cg_iterations, cgi);
+      if (cgi >= 3) ++cnt.subproblems_of_3_cg_iterations;
       if (rho > c.acceptance_threshold) {
         x = xt; f = ft; g = gt; nfev += 1;
         obj.hessian(x, H);
@@ -260,7 +295,12 @@ inline void solve_one(const Objective& obj, Order order, int W, const tr_stop& s
       const double scale = st.gradient_norm_relative ? std::max(1.0, o.amax(x)) : 1.0;
       if (gnorm < st.gradient_norm * scale) { status = kGradient; decided = true; }
     }
-    if (!decided && condition_stop > 0 && condition(H, n) > condition_stop) status = kCondition;
+    if (!decided && condition_stop > 0) {
+      const double cond = condition(H, n);
+      ++cnt.conditions;
+      cnt.min_condition_margin = std::min(cnt.min_condition_margin, std::fabs(cond - condition_stop) / condition_stop);
+      if (cond > condition_stop) status = kCondition;
+    }
   } while (status == kContinue);
   for (int j = 0; j < n; ++j) {
     x_out[j] = x[j];
@@ -274,6 +314,7 @@ inline void solve_one(const Objective& obj, Order order, int W, const tr_stop& s
   prog->x_delta = x_delta;
   prog->f_delta = f_delta;
   prog->gradient_norm = gnorm;
+  if (counters) *counters = cnt;
 }
 
 }  // namespace tr_twin
