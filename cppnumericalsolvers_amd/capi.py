@@ -118,6 +118,24 @@ class ArmijoConfig(C.Structure):
     _fields_ = [("c", C.c_double), ("rho", C.c_double), ("alpha_min", C.c_double)]
 
 
+# ... and the derivative checker's (checked by tests/test_derivatives_twin.py)
+DERIVATIVE_SYMBOLS = ["mi355_derivative_default_config", "mi355_check_derivatives_batch",
+                      "mi355_check_derivatives_batch_host"]
+
+
+class DerivativeConfig(C.Structure):
+    """mi355_derivative_config: stencils, and the step / tolerance overrides (0 = the reference's)."""
+    _fields_ = [("gradient_accuracy", C.c_int32), ("hessian_accuracy", C.c_int32), ("gradient_step", C.c_double),
+                ("hessian_step", C.c_double), ("gradient_tolerance", C.c_double), ("hessian_tolerance", C.c_double)]
+
+
+# mi355_derivative_report as a numpy record (40 bytes, natural alignment)
+DERIVATIVE_REPORT_DTYPE = np.dtype(
+    [("gradient_ok", "<i4"), ("hessian_ok", "<i4"), ("gradient_worst_index", "<i4"), ("hessian_worst_index", "<i4"),
+     ("nonfinite", "<i4"), ("pad", "<i4"), ("gradient_worst_excess", "<f8"), ("hessian_worst_excess", "<f8")], align=True)
+assert DERIVATIVE_REPORT_DTYPE.itemsize == 40 and C.sizeof(DerivativeConfig) == 40
+
+
 class Desc(C.Structure):
     """mi355_lbfgs_desc."""
     _fields_ = [
@@ -275,6 +293,10 @@ def _bind(L):
                                                                    C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mi355_conjugated_gradient_descent_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), C.POINTER(ArmijoConfig),
                                                                         C.c_int64, vp, vp, vp, vp, vp]
+    L.mi355_derivative_default_config.argtypes = [C.POINTER(DerivativeConfig)]
+    L.mi355_check_derivatives_batch.argtypes = [vp, C.POINTER(Desc), C.POINTER(DerivativeConfig), C.c_int64] + [vp] * 8
+    L.mi355_check_derivatives_batch_host.argtypes = [vp, C.POINTER(Desc), C.POINTER(DerivativeConfig),
+                                                     C.c_int64] + [vp] * 7
     L.mi355_lbfgsb_minimize_batch.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mi355_lbfgsb_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, vp, vp, vp, vp, vp]
     L.mi355_lbfgs_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -373,6 +395,17 @@ def default_armijo_config(**overrides):
     for k, v in overrides.items():
         if not hasattr(c, k):
             raise TypeError("Armijo config has no field %r" % k)
+        setattr(c, k, v)
+    return c
+
+
+def default_derivative_config(**overrides):
+    """mi355_derivative_default_config(), with the named fields replaced."""
+    c = DerivativeConfig()
+    check(load().mi355_derivative_default_config(C.byref(c)))
+    for k, v in overrides.items():
+        if not hasattr(c, k):
+            raise TypeError("derivative config has no field %r" % k)
         setattr(c, k, v)
     return c
 

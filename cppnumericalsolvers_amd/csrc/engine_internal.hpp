@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/mi355_lbfgs.h"
+#include "derivative_check_config.hpp"
 #include "first_order_config.hpp"
 #include "lbfgs_kernel.hpp"
 #include "lbfgsb_kernel.hpp"
@@ -257,6 +258,27 @@ void register_user_first_order(int objective_id, UserFirstOrderFn fn);
 UserFirstOrderFn user_first_order(int objective_id);
 struct UserFirstOrderRegistration {
   UserFirstOrderRegistration(int objective_id, UserFirstOrderFn fn) { register_user_first_order(objective_id, fn); }
+};
+
+// The derivative checker (dispatch_derivatives.hip, derivative_check_kernel.hpp): phase = a DerivativePhase, W lanes per
+// point, E coordinates per lane (1 for the Hessian phases)
+int dispatch_derivatives(mi355_lbfgs_ctx* ctx, int phase, int W, int E, int objective, const DerivativeArgs& args,
+                         hipStream_t stream);
+// kDerivativeHasEval | kDerivativeHasHessFull of the objective's functor; -1: this library holds no derivative kernel for it
+int derivative_capabilities_of(int objective);
+const char* derivative_unsupported_message(int objective);
+int derivative_report_init(mi355_derivative_report* report, long long B, hipStream_t stream);
+int derivative_compare(const DerivativeCompareArgs& args, bool hessian, hipStream_t stream);
+// ... on a user functor: registered by the unit _build.py generates for derivatives=True
+using UserDerivativesFn = int (*)(mi355_lbfgs_ctx* ctx, int phase, int W, int E, const DerivativeArgs& args,
+                                  hipStream_t stream);
+void register_user_derivatives(int objective_id, UserDerivativesFn fn, int capabilities);
+UserDerivativesFn user_derivatives(int objective_id);
+int user_derivatives_capabilities(int objective_id);
+struct UserDerivativesRegistration {
+  UserDerivativesRegistration(int objective_id, UserDerivativesFn fn, int capabilities) {
+    register_user_derivatives(objective_id, fn, capabilities);
+  }
 };
 
 // desc->trace (device array pointers) -> the trace fields of SolveArgs; uploads the problem list, zeroes `written`

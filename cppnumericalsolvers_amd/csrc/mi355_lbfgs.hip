@@ -32,6 +32,8 @@ struct UserEntry {
   UserNelderMeadFn nelder_mead = nullptr;
   UserNewtonDescentFn newton_descent = nullptr;
   UserFirstOrderFn first_order = nullptr;
+  UserDerivativesFn derivatives = nullptr;
+  int derivatives_capabilities = 0;
   std::string name;
 };
 std::vector<std::pair<int, UserEntry>>& user_table() {
@@ -132,6 +134,30 @@ UserFirstOrderFn user_first_order(int objective_id) {
   for (auto& e : user_table())
     if (e.first == objective_id) return e.second.first_order;
   return nullptr;
+}
+void register_user_derivatives(int objective_id, UserDerivativesFn fn, int capabilities) {
+  if (objective_id < MI355_OBJ_USER_FIRST) return;
+  for (auto& e : user_table()) {
+    if (e.first == objective_id) {
+      e.second.derivatives = fn;
+      e.second.derivatives_capabilities = capabilities;
+      return;
+    }
+  }
+  UserEntry u;
+  u.derivatives = fn;
+  u.derivatives_capabilities = capabilities;
+  user_table().emplace_back(objective_id, u);
+}
+UserDerivativesFn user_derivatives(int objective_id) {
+  for (auto& e : user_table())
+    if (e.first == objective_id) return e.second.derivatives;
+  return nullptr;
+}
+int user_derivatives_capabilities(int objective_id) {
+  for (auto& e : user_table())
+    if (e.first == objective_id) return e.second.derivatives_capabilities;
+  return 0;
 }
 static const UserEntry* find_user_objective(int objective_id) {
   for (auto& e : user_table())
@@ -1650,4 +1676,204 @@ extern "C" int mi355_conjugated_gradient_descent_minimize_batch(mi355_lbfgs_ctx*
                                                                 void* stream) {
   return first_order_minimize_batch("ConjugatedGradientDescent", kConjugatedGradientDescent, ctx, desc, config, B, x0,
                                     x_out, f_out, g_out, progress_out, stream);
+}
+
+// ---- derivative check of a device functor (derivative_check_kernel.hpp) ----------------------------------------------
+extern "C" int mi355_derivative_default_config(mi355_derivative_config* out) {
+  if (!out) return fail(MI355_ERR_INVALID_ARGUMENT, "null config");
+  out->gradient_accuracy = 3;   // utils/derivatives.h:257
+  out->hessian_accuracy = 3;    // :285
+  out->gradient_step = out->hessian_step = 0.0;
+  out->gradient_tolerance = out->hessian_tolerance = 0.0;
+  return MI355_OK;
+}
+
+static_assert(sizeof(mi355_derivative_config) == 40, "mi355_derivative_config layout");
+static_assert(sizeof(mi355_derivative_report) == 40, "mi355_derivative_report layout");
+
+extern "C" int mi355_check_derivatives_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc_in,
+                                             const mi355_derivative_config* config, int64_t B, const double* x,
+                                             double* f_out, double* grad_out, double* grad_fd_out, double* hess_out,
+                                             double* hess_fd_out, mi355_derivative_report* report_out, void* stream_) {
+  if (!desc_in) return fail(MI355_ERR_INVALID_ARGUMENT, "null desc");
+  // only the objective, n, lanes_per_problem, the parameter fields and arithmetic are read
+  mi355_lbfgs_desc desc = *desc_in;
+  desc.m = 1;
+  desc.linesearch = MI355_LS_MORE_THUENTE;
+  desc.history_placement = 0;
+  desc.hessian_from_functor = 0;
+  desc.hessian_diagonal = nullptr;
+  desc.hessian_condition_stop = 0.0;
+  std::memset(&desc.stop, 0, sizeof(desc.stop));
+  const bool want_hessian = hess_out != nullptr || hess_fd_out != nullptr;
+  if (desc.n > MI355_LBFGS_MAX_N)
+    return fail(MI355_ERR_UNSUPPORTED,
+                "derivative check: the gradient is built for n <= 256 (x in registers, up to four coordinates per lane)");
+  if (want_hessian && desc.n > 64)
+    return fail(MI355_ERR_UNSUPPORTED,
+                "derivative check: the Hessian is built for n <= 64 (one coordinate per lane, H in the segment's LDS); pass "
+                "hess_out = hess_fd_out = NULL for the gradient alone");
+  int rc = validate(ctx, &desc, B);
+  if (rc != MI355_OK) return rc;
+  if (desc.arithmetic == MI355_ARITH_FMA)
+    return fail(MI355_ERR_UNSUPPORTED, "the derivative check is built for the exact arithmetic only (no MI355_ARITH_FMA)");
+  const int caps = derivative_capabilities_of(desc.objective);
+  if (caps < 0) return fail(MI355_ERR_UNSUPPORTED, derivative_unsupported_message(desc.objective));
+  const bool has_eval = (caps & kDerivativeHasEval) != 0, has_hess = (caps & kDerivativeHasHessFull) != 0;
+  if (grad_out != nullptr && !has_eval)
+    return fail(MI355_ERR_UNSUPPORTED,
+                "derivative check: this functor has no eval (value-only): it has no analytic gradient to return or to "
+                "check; pass grad_out = NULL for the finite-difference gradient alone");
+  if (hess_out != nullptr && !has_hess)
+    return fail(MI355_ERR_UNSUPPORTED,
+                "derivative check: this functor has no hess_full: it has no analytic Hessian to return or to check; pass "
+                "hess_out = NULL for the finite-difference Hessian alone");
+  mi355_derivative_config c;
+  mi355_derivative_default_config(&c);
+  if (config) c = *config;
+  if (c.gradient_accuracy < 0 || c.gradient_accuracy > 3 || c.hessian_accuracy < 0 || c.hessian_accuracy > 3)
+    return fail(MI355_ERR_INVALID_ARGUMENT, "derivative check: the accuracies must be 0, 1, 2 or 3");
+  if (!(c.gradient_step >= 0.0) || !(c.hessian_step >= 0.0) || !(c.gradient_tolerance >= 0.0) ||
+      !(c.hessian_tolerance >= 0.0))
+    return fail(MI355_ERR_INVALID_ARGUMENT, "derivative check: steps and tolerances must be >= 0 (0 = the reference's)");
+  int W = desc.lanes_per_problem;
+  if (W == 0) {
+    W = 8;
+    while (W < desc.n && W < 64) W <<= 1;
+  } else if (!(W == 8 || W == 16 || W == 32 || W == 64)) {
+    return fail(MI355_ERR_INVALID_ARGUMENT, "derivative check: lanes_per_problem must be 0, 8, 16, 32 or 64");
+  }
+  const int E = (desc.n <= W) ? 1 : ((desc.n <= 2 * W) ? 2 : 4);
+  if ((E != 1 && W != 64) || W * E < desc.n)
+    return fail(MI355_ERR_INVALID_ARGUMENT,
+                "derivative check: the mapping must cover n with 8, 16, 32 or 64 lanes at one coordinate per lane, or 64 "
+                "lanes at two or four");
+  if (B == 0) return MI355_OK;
+  if (!x) return fail(MI355_ERR_INVALID_ARGUMENT, "null x");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MI355_ENTER_DEVICE(ctx);
+  rc = upload_params(ctx, &desc, W, E, stream);
+  if (rc != MI355_OK) return rc;
+
+  // a report needs both sides of a comparison: a side the caller did not ask for goes to a temporary
+  const size_t bn = static_cast<size_t>(B) * desc.n * sizeof(double);
+  const bool report_gradient = report_out != nullptr && has_eval;
+  const bool report_hessian = report_out != nullptr && want_hessian && has_hess;
+  double* temporaries[4] = {nullptr, nullptr, nullptr, nullptr};
+  auto release = [&]() {
+    bool any = false;
+    for (double* t : temporaries) any = any || t != nullptr;
+    if (any) (void)hipStreamSynchronize(stream);
+    for (double*& t : temporaries) {
+      if (t) (void)hipFree(t);
+      t = nullptr;
+    }
+  };
+  auto temporary = [&](int slot, double*& p, size_t bytes) -> hipError_t {
+    if (p != nullptr) return hipSuccess;
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&temporaries[slot]), bytes);
+    p = temporaries[slot];
+    return e;
+  };
+  hipError_t he = hipSuccess;
+  if (report_gradient) {
+    he = temporary(0, grad_out, bn);
+    if (he == hipSuccess) he = temporary(1, grad_fd_out, bn);
+  }
+  if (he == hipSuccess && report_hessian) {
+    he = temporary(2, hess_out, bn * desc.n);
+    if (he == hipSuccess) he = temporary(3, hess_fd_out, bn * desc.n);
+  }
+  if (he != hipSuccess) {
+    release();
+    return fail(MI355_ERR_HIP, std::string("derivative check: temporary arrays: ") + hipGetErrorString(he));
+  }
+
+  DerivativeArgs args;
+  std::memset(&args, 0, sizeof(args));
+  args.x = x;
+  args.f_out = f_out;
+  args.grad_out = grad_out;
+  args.grad_fd_out = grad_fd_out;
+  args.hess_out = hess_out;
+  args.hess_fd_out = hess_fd_out;
+  args.obj_params = ctx->params_dev;
+  args.per_problem = desc.per_problem_data;
+  args.per_problem_stride = desc.per_problem_stride;
+  args.B = B;
+  args.n = desc.n;
+  args.gradient_accuracy = c.gradient_accuracy;
+  args.hessian_accuracy = c.hessian_accuracy;
+  args.gradient_step = c.gradient_step > 0.0 ? c.gradient_step : kDerivativeSqrtEps;
+  args.hessian_step = c.hessian_step > 0.0 ? c.hessian_step : kDerivativeSqrtEps;
+  rc = MI355_OK;
+  if (f_out != nullptr || grad_out != nullptr || grad_fd_out != nullptr)
+    rc = dispatch_derivatives(ctx, kDerivativeGradient, W, E, desc.objective, args, stream);
+  if (rc == MI355_OK && hess_out != nullptr)
+    rc = dispatch_derivatives(ctx, kDerivativeHessian, W, 1, desc.objective, args, stream);
+  if (rc == MI355_OK && hess_fd_out != nullptr)
+    rc = dispatch_derivatives(ctx, kDerivativeFiniteHessian, W, 1, desc.objective, args, stream);
+  if (rc == MI355_OK && report_out != nullptr) rc = derivative_report_init(report_out, B, stream);
+  if (rc == MI355_OK && report_gradient) {
+    DerivativeCompareArgs cmp;
+    cmp.actual = grad_out;
+    cmp.expected = grad_fd_out;
+    cmp.report = report_out;
+    cmp.B = B;
+    cmp.count = desc.n;
+    cmp.tol = c.gradient_tolerance > 0.0 ? c.gradient_tolerance : static_cast<double>(1e-2f);   // :258
+    rc = derivative_compare(cmp, false, stream);
+  }
+  if (rc == MI355_OK && report_hessian) {
+    DerivativeCompareArgs cmp;
+    cmp.actual = hess_out;
+    cmp.expected = hess_fd_out;
+    cmp.report = report_out;
+    cmp.B = B;
+    cmp.count = desc.n * desc.n;
+    cmp.tol = c.hessian_tolerance > 0.0 ? c.hessian_tolerance : static_cast<double>(1e-1f);     // :286
+    rc = derivative_compare(cmp, true, stream);
+  }
+  release();
+  return rc;
+}
+
+extern "C" int mi355_check_derivatives_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
+                                                  const mi355_derivative_config* config, int64_t B, const double* x,
+                                                  double* f_out, double* grad_out, double* grad_fd_out, double* hess_out,
+                                                  double* hess_fd_out, mi355_derivative_report* report_out) {
+  if (!ctx || !desc) return fail(MI355_ERR_INVALID_ARGUMENT, "null context / desc");
+  if (B <= 0 || !x || desc->n < 1 || desc->n > MI355_LBFGS_MAX_N)   // (the device entry point words the refusals)
+    return mi355_check_derivatives_batch(ctx, desc, config, B, x, f_out, grad_out, grad_fd_out, hess_out, hess_fd_out,
+                                         report_out, nullptr);
+  if (desc->per_problem_data != nullptr)
+    return fail(MI355_ERR_UNSUPPORTED, "the host-pointer derivative check takes objectives without per-problem data");
+  MI355_ENTER_DEVICE(ctx);
+  const size_t n = static_cast<size_t>(desc->n), b = static_cast<size_t>(B);
+  // one device block: x | f | grad | grad_fd | hess | hess_fd | report, each present where the caller asked for it
+  const size_t sizes[7] = {b * n * 8, f_out ? b * 8 : 0, grad_out ? b * n * 8 : 0, grad_fd_out ? b * n * 8 : 0,
+                           hess_out ? b * n * n * 8 : 0, hess_fd_out ? b * n * n * 8 : 0,
+                           report_out ? b * sizeof(mi355_derivative_report) : 0};
+  size_t offsets[7], total = 0;
+  for (int k = 0; k < 7; ++k) {
+    offsets[k] = total;
+    total += (sizes[k] + 255) / 256 * 256;
+  }
+  char* block = nullptr;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&block), total));
+  auto at = [&](int k) -> void* { return sizes[k] ? block + offsets[k] : nullptr; };
+  void* const outs[7] = {nullptr, f_out, grad_out, grad_fd_out, hess_out, hess_fd_out, report_out};
+  hipError_t he = hipMemcpy(block, x, sizes[0], hipMemcpyHostToDevice);
+  int rc = MI355_OK;
+  if (he == hipSuccess)
+    rc = mi355_check_derivatives_batch(ctx, desc, config, B, static_cast<const double*>(at(0)),
+                                       static_cast<double*>(at(1)), static_cast<double*>(at(2)),
+                                       static_cast<double*>(at(3)), static_cast<double*>(at(4)),
+                                       static_cast<double*>(at(5)), static_cast<mi355_derivative_report*>(at(6)), nullptr);
+  if (he == hipSuccess && rc == MI355_OK) he = hipStreamSynchronize(nullptr);
+  for (int k = 1; k < 7 && he == hipSuccess && rc == MI355_OK; ++k)
+    if (sizes[k]) he = hipMemcpy(outs[k], at(k), sizes[k], hipMemcpyDeviceToHost);
+  (void)hipFree(block);
+  if (he != hipSuccess) return fail(MI355_ERR_HIP, std::string("derivative check (host): ") + hipGetErrorString(he));
+  return rc;
 }

@@ -1106,6 +1106,68 @@ class BatchedAugmentedLagrangian:
         return f, g
 
 
+@dataclass
+class DerivativeCheck:
+    """What check_derivatives returns: device tensors.  f [B], grad / grad_fd [B, n] (the functor's gradient, the
+    finite-difference one), hess / hess_fd [B, n, n] (entry [b, j, i] is H(i, j): column major, as hess_full writes it;
+    None without hessian=True) and the fields of mi355_derivative_report as [B] tensors."""
+    f: object
+    grad: object
+    grad_fd: object
+    hess: object
+    hess_fd: object
+    gradient_ok: object
+    hessian_ok: object
+    gradient_worst_index: object
+    hessian_worst_index: object
+    nonfinite: object
+    gradient_worst_excess: object
+    hessian_worst_excess: object
+    report: object   # the raw records: uint8 [B * 40], capi.DERIVATIVE_REPORT_DTYPE
+
+
+def check_derivatives(objective, x, *, hessian=True, accuracy=3, gradient_step=0.0, hessian_step=0.0,
+                      gradient_tolerance=0.0, hessian_tolerance=0.0, lanes_per_problem=0, context=None):
+    """The reference's IsGradientCorrect / IsHessianCorrect (utils/derivatives.h) on the DEVICE functor of `objective`
+    at every row of x ([B, n] float64 CUDA tensor): mi355_check_derivatives_batch.  Steps and tolerances of 0 are the
+    reference's (h = 2^-26 max(|x_d|, 1), 1e-2f, 1e-1f); hessian_step=2**-13 makes the Hessian check usable away from
+    a minimiser, where the reference's step drowns the second difference in rounding noise.
+    Asynchronous on the current stream.  Returns a DerivativeCheck."""
+    import torch
+    if x.dtype != torch.float64 or x.dim() != 2 or not x.is_cuda:
+        raise ValueError("x must be a [B, n] float64 CUDA tensor")
+    ctx = context or Context(x.device.index or 0)
+    if x.device != torch.device("cuda", ctx.device):
+        raise ValueError("x lives on %s, the context on cuda:%d" % (x.device, ctx.device))
+    x = x.contiguous()
+    B, n = x.shape
+    d = capi.Desc()
+    d.objective = objective.objective_id
+    d.n = int(n)
+    d.m = 1
+    p = np.ascontiguousarray(objective.params, dtype=np.float64)
+    d.objective_params = p.ctypes.data_as(C.POINTER(C.c_double)) if p.size else None
+    d.n_params = int(p.size)
+    d.lanes_per_problem = int(lanes_per_problem)
+    c = capi.DerivativeConfig(int(accuracy), int(accuracy), float(gradient_step), float(hessian_step),
+                              float(gradient_tolerance), float(hessian_tolerance))
+    f = torch.empty(B, dtype=torch.float64, device=x.device)
+    grad, grad_fd = torch.empty_like(x), torch.empty_like(x)
+    hess = torch.empty(B, n, n, dtype=torch.float64, device=x.device) if hessian else None
+    hess_fd = torch.empty_like(hess) if hessian else None
+    report = torch.empty(B * capi.DERIVATIVE_REPORT_DTYPE.itemsize, dtype=torch.uint8, device=x.device)
+    capi.check(ctx._lib.mi355_check_derivatives_batch(
+        ctx.handle, C.byref(d), C.byref(c), B, x.data_ptr(), f.data_ptr(), grad.data_ptr(), grad_fd.data_ptr(),
+        hess.data_ptr() if hessian else None, hess_fd.data_ptr() if hessian else None, report.data_ptr(),
+        C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+    ints = report.view(torch.int32).view(B, 10)
+    doubles = report.view(torch.float64).view(B, 5)
+    out = DerivativeCheck(f, grad, grad_fd, hess, hess_fd, ints[:, 0], ints[:, 1], ints[:, 2], ints[:, 3], ints[:, 4],
+                          doubles[:, 3], doubles[:, 4], report)
+    out._keepalive = (p, ctx)   # (the call is asynchronous: the blob and a context made here outlive it with the result)
+    return out
+
+
 def al_progress_to_numpy(prog):
     """Device progress bytes of BatchedAugmentedLagrangian.minimize -> numpy records (capi.AL_PROGRESS_DTYPE)."""
     return prog.cpu().numpy().view(capi.AL_PROGRESS_DTYPE)

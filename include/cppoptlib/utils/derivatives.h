@@ -6,7 +6,9 @@
 // 0..3, step h = sqrt(eps) max(|x_d|, 1) per coordinate, and the two checkers with the reference's tolerances
 // (1e-2 and 1e-1 relative to max(1, |actual|, |expected|)).  A user calls them before handing a function to a solver,
 // i.e. before anything reaches the GPU: they evaluate the HOST operator() of the function (or of whatever a type-erased
-// FunctionExpr wraps) and are not part of the device path.
+// FunctionExpr wraps) and are not part of the device path.  The same four checks on the function's DEVICE twin — the
+// functor a solve actually evaluates — and CheckDeviceTwin, the comparison of that twin with this operator(), are in
+// ../mi355/derivatives.h (ComputeFiniteGradientOnDevice, ..., IsHessianCorrectOnDevice).
 #ifndef INCLUDE_CPPOPTLIB_UTILS_DERIVATIVES_H_
 #define INCLUDE_CPPOPTLIB_UTILS_DERIVATIVES_H_
 

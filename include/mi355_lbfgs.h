@@ -559,6 +559,63 @@ int mi355_conjugated_gradient_descent_minimize_batch_host(mi355_lbfgs_ctx* ctx, 
                                                           const double* x0, double* x_out, double* f_out, double* g_out,
                                                           mi355_lbfgs_progress* progress_out);
 
+/* ---- derivative check of a device functor -------------------------------------------------------------------------
+ * The device counterpart of utils/derivatives.h of the reference (ComputeFiniteGradient :37-83, ComputeFiniteHessian
+ * :86-252, IsGradientCorrect :254-280, IsHessianCorrect :282-311), run on the DEVICE functor — the eval / value /
+ * hess_full a solve actually evaluates — at B points at once.  A step or tolerance of 0 means the reference's:
+ * h = sqrt(eps) max(|x_d|, 1) with sqrt(eps) = 2^-26, tolerances 1e-2f (gradient) and 1e-1f (Hessian) widened to double.
+ * With h = sqrt(eps) the second difference carries rounding noise of order eps |f| / h^2 = |f|: the reference's own
+ * Hessian check FAILS on a correct Hessian wherever |f| is large (Rosenbrock at an ordinary start: 10-18 times the
+ * tolerance) and passes next to a minimiser; hessian_step = 2^-13 (eps^(1/4)) makes it usable everywhere (DESIGN.md
+ * section 4.10 has the figures). */
+typedef struct mi355_derivative_config {
+  int32_t gradient_accuracy;  /* 0..3: the 2, 4, 6, 8 point stencil (default 3, as IsGradientCorrect) */
+  int32_t hessian_accuracy;   /* 0: the four corners; 1..3: the sixteen-point formula (default 3, as IsHessianCorrect) */
+  double gradient_step;       /* factor of max(|x_d|, 1); 0 = 2^-26 */
+  double hessian_step;
+  double gradient_tolerance;  /* 0 = (double)1e-2f */
+  double hessian_tolerance;   /* 0 = (double)1e-1f */
+} mi355_derivative_config;
+int mi355_derivative_default_config(mi355_derivative_config* out);
+
+/* Per point.  The test of an entry is |a - e| > tol max(max(|a|, |e|), 1), a = the functor's, e = the finite
+ * difference; excess = |a - e| / (tol scale), above 1 = failed.  A NaN on either side makes the comparison false, so
+ * the entry PASSES, as in the reference (reproduced, not repaired); so does an infinite entry.  Entries with a NaN or
+ * an infinity on either side are counted in `nonfinite` (gradient and Hessian together) and take no part in the worst
+ * excess.  worst_index: the first entry with the worst excess — the coordinate, or the position in the column-major
+ * n x n array (row + n * column); -1 where no entry was comparable. */
+typedef struct mi355_derivative_report {
+  int32_t gradient_ok;  /* 1 / 0; -1: not checked */
+  int32_t hessian_ok;   /* 1 / 0; -1: not checked */
+  int32_t gradient_worst_index;
+  int32_t hessian_worst_index;
+  int32_t nonfinite;
+  int32_t pad;
+  double gradient_worst_excess;
+  double hessian_worst_excess;
+} mi355_derivative_report;
+
+/* x [B][n] -> f_out [B], grad_out / grad_fd_out [B][n] (the functor's gradient, the finite-difference one), hess_out /
+ * hess_fd_out [B][n][n] (the functor's Hessian as hess_full writes it, column major; the finite-difference one),
+ * report_out [B].  Device pointers; any output may be NULL; both Hessian outputs NULL (and, with a report, that is all
+ * it takes) means gradient only.  A report needs both sides of a comparison: where one of the two arrays is NULL the
+ * call computes it into a temporary of its own and waits for the stream before it returns.  config NULL = defaults.
+ * Of desc only objective, n, lanes_per_problem (0 = the padded width; a wider one gives the same bits), the parameter
+ * fields (objective_params, n_params, per_problem_data, per_problem_stride) and arithmetic are read.
+ * Gradient: n <= 256 (8, 16, 32, 64 lanes at one coordinate per lane, 64 lanes at two and four); Hessian: n <= 64, one
+ * coordinate per lane.  Objectives: Rosenbrock, DiagQuadratic, user functors built with derivatives=True; a functor
+ * without hess_full has no hess_out, a functor without eval (value-only) no grad_out: MI355_ERR_UNSUPPORTED with the
+ * reason, as for the objectives with LDS data, n above the caps and MI355_ARITH_FMA. */
+int mi355_check_derivatives_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
+                                  const mi355_derivative_config* config, int64_t B, const double* x, double* f_out,
+                                  double* grad_out, double* grad_fd_out, double* hess_out, double* hess_fd_out,
+                                  mi355_derivative_report* report_out, void* stream);
+/* The same with host arrays, synchronous. */
+int mi355_check_derivatives_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
+                                       const mi355_derivative_config* config, int64_t B, const double* x,
+                                       double* f_out, double* grad_out, double* grad_fd_out, double* hess_out,
+                                       double* hess_fd_out, mi355_derivative_report* report_out);
+
 /* Duration in ms of the most recent solve kernel on this context, measured with
  * HIP events recorded on the launch stream; blocks until that kernel finished. */
 int mi355_lbfgs_last_kernel_ms(mi355_lbfgs_ctx* ctx, float* ms);
