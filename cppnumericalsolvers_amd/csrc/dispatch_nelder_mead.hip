@@ -6,14 +6,24 @@
 #include "nelder_mead_launch.hpp"
 
 namespace mi355 {
+namespace {
+template <int W, int E>
+struct RosenbrockOf {
+  using type = RosenbrockObjective;
+};
+template <int W, int E>
+struct DiagQuadraticOf {
+  using type = DiagQuadraticObjective<E>;
+};
+}  // namespace
 
 int dispatch_nelder_mead(mi355_lbfgs_ctx* ctx, int W, int objective, const SolveArgs& args,
                          const NelderMeadDeviceConfig& cfg, hipStream_t stream) {
   switch (objective) {
     case MI355_OBJ_ROSENBROCK:
-      return launch_nelder_mead_w<RosenbrockObjective>(ctx, W, args, cfg, stream);
+      return launch_nelder_mead_w<RosenbrockOf>(ctx, W, args, cfg, stream);
     case MI355_OBJ_DIAG_QUADRATIC:
-      return launch_nelder_mead_w<DiagQuadraticObjective<1>>(ctx, W, args, cfg, stream);
+      return launch_nelder_mead_w<DiagQuadraticOf>(ctx, W, args, cfg, stream);
   }
   if (objective >= MI355_OBJ_USER_FIRST) {
     const UserNelderMeadFn fn = user_nelder_mead(objective);

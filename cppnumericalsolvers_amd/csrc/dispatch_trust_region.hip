@@ -6,14 +6,24 @@
 #include "trust_region_launch.hpp"
 
 namespace mi355 {
+namespace {
+template <int W, int E>
+struct RosenbrockOf {
+  using type = RosenbrockConditionObjective;
+};
+template <int W, int E>
+struct DiagQuadraticOf {
+  using type = DiagQuadraticHessObjective<E>;
+};
+}  // namespace
 
 int dispatch_trust_region(mi355_lbfgs_ctx* ctx, int W, int objective, const SolveArgs& args,
                           const TrustRegionDeviceConfig& cfg, hipStream_t stream) {
   switch (objective) {
     case MI355_OBJ_ROSENBROCK:
-      return launch_trust_region_w<RosenbrockConditionObjective>(ctx, W, args, cfg, stream);
+      return launch_trust_region_w<RosenbrockOf>(ctx, W, args, cfg, stream);
     case MI355_OBJ_DIAG_QUADRATIC:
-      return launch_trust_region_w<DiagQuadraticHessObjective<1>>(ctx, W, args, cfg, stream);
+      return launch_trust_region_w<DiagQuadraticOf>(ctx, W, args, cfg, stream);
   }
   if (objective >= MI355_OBJ_USER_FIRST) {
     const UserTrustRegionFn fn = user_trust_region(objective);

@@ -8,7 +8,7 @@
 //   ConjugatedGradientDescent::InitializeSolver / OptimizationStep
 //                                                solver/conjugated_gradient_descent.h:62-85 (Method 1)
 //   Armijo<F, 1>::Search                         linesearch/armijo.h:45-64
-//   Progress::Update                             solver/progress.h:153-327                  (progress_device.hpp)
+//   Progress::Update                             solver/progress.h:153-327                  (solver_driver.hpp)
 //
 // Mapping.  A problem of dimension n <= W * E is owned by a segment of W consecutive lanes, E coordinates per lane
 // (coordinate j = sl * E + e, as the Lbfgs kernels); x, g, d and the previous iterate are registers.  No per-problem LDS.
@@ -48,7 +48,7 @@
 #include "lbfgs_kernel.hpp"
 #include "more_thuente_device.hpp"
 #include "objectives.hpp"
-#include "progress_device.hpp"
+#include "solver_driver.hpp"
 #include "wave_primitives.hpp"
 
 namespace mi355 {
@@ -61,49 +61,33 @@ struct HasValueOnly<Obj, W, E,
                     std::void_t<decltype(std::declval<const Obj&>().template value<W, E>(
                         std::declval<const double (&)[E]>(), 0, 0))>> : std::true_type {};
 
-// v, or the canonical quiet NaN where v is one (see "NaN results" at the head of this file)
-__device__ __forceinline__ double canonical_nan(double v) { return (v != v) ? __builtin_nan("") : v; }
-
 template <int W, int E, int Method, class Obj>
 __global__ __launch_bounds__(64) void first_order_kernel(const SolveArgs a, const FirstOrderDeviceConfig cfg) {
   static_assert(Obj::kLdsDoubles == 0 && Obj::shared_lds_doubles() == 0,
                 "the first-order kernel is built for functors without LDS data");
   static_assert(Method == kGradientDescent || Method == kConjugatedGradientDescent, "Method");
-  constexpr int kSegs = kWave / W;
-  constexpr double eps = 2.220446049250313e-16;
 
   const int lane = threadIdx.x & (kWave - 1);
   const int seg = lane / W;
   const int sl = lane % W;
   const int n = a.n;
-  const long long queue_length = a.count_dev ? static_cast<long long>(*a.count_dev) : a.B;
-  // plateau ring of stop.past > 0: one MAX_PAST slot per resident segment in global scratch
-  double* const past_f =
-      a.scratch + (static_cast<size_t>(blockIdx.x) * kSegs + seg) * MI355_LBFGS_MAX_PAST;
+  const long long queue_length = queue_length_of(a);
+  double* const past_f = plateau_ring_slot<W>(a, seg);
 
   Obj obj;
   obj.load(a.obj_params, n, sl, nullptr, nullptr);
 
   double x[E], g[E], d[E], xprev[E];
   double f = 0.0, gg_prev = 0.0;
-  unsigned nfev = 0, trials_total = 0, num_iterations = 0;
-  int x_delta_violations = 0, f_delta_violations = 0, status = MI355_STATUS_NOT_STARTED;
-  double x_delta = 0.0, f_delta = 0.0, gradient_norm = 0.0, xinf_bound = 0.0;
-  bool past_init = false;
-  int past_pos = 0;
+  SolveProgress prog;                                      // prog.sum_k: the trial evaluations
   long long prob = 0;
   bool need_fetch = true;
 
   while (true) {
     if (need_fetch) {
-      // ---- next unsolved problem from the queue ---------------------------------
-      unsigned long long nxt = 0;
-      if (sl == 0) nxt = atomicAdd(a.next_problem, 1ULL);
-      const unsigned lo = static_cast<unsigned>(seg_bcast_first<W>(static_cast<int>(nxt & 0xffffffffULL)));
-      const unsigned hi = static_cast<unsigned>(seg_bcast_first<W>(static_cast<int>(nxt >> 32)));
-      prob = static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo);
-      if (prob >= queue_length) break;
-      if (a.problem_map != nullptr) prob = a.problem_map[prob];
+      bool drained;
+      prob = fetch_problem<W>(a, queue_length, sl, drained);
+      if (drained) break;
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         const int j = sl * E + e;
@@ -115,23 +99,15 @@ __global__ __launch_bounds__(64) void first_order_kernel(const SolveArgs a, cons
       // Solver::Minimize prologue (solver.h:189-192), Progress reset
       f = obj.template eval<W, E>(x, g, n, sl);
       // Method 1: InitializeSolver evaluates function(x0, &previous_gradient_) (:62-65): counted, the gradient is g
-      nfev = (Method == kConjugatedGradientDescent) ? 2 : 1;
+      prog.reset<W, E>((Method == kConjugatedGradientDescent) ? 2 : 1, x);
       gg_prev = 0.0;
-      trials_total = 0;
-      num_iterations = 0;
-      x_delta_violations = f_delta_violations = 0;
-      x_delta = f_delta = gradient_norm = 0.0;
-      status = MI355_STATUS_NOT_STARTED;
-      past_init = false;
-      past_pos = 0;
-      xinf_bound = seg_amax<W, E>(x);
     }
 
     const double fprev = f;
 #pragma unroll
     for (int e = 0; e < E; ++e) xprev[e] = x[e];
     unsigned trials = 0;
-    nfev += 2;   // function(current.x, &gradient) of OptimizationStep, and the search's own evaluation at x
+    prog.nfev += 2;   // function(current.x, &gradient) of OptimizationStep, and the search's own evaluation at x
     const double gg = seg_dot<W, E>(g, g);
     if constexpr (Method == kGradientDescent) {
       // ================ GradientDescent::OptimizationStep (gradient_descent.h:64-73) ================
@@ -146,7 +122,7 @@ __global__ __launch_bounds__(64) void first_order_kernel(const SolveArgs a, cons
       }
     } else {
       // ========== ConjugatedGradientDescent::OptimizationStep (conjugated_gradient_descent.h:67-85) ==========
-      if (num_iterations == 0) {
+      if (prog.num_iterations == 0) {
 #pragma unroll
         for (int e = 0; e < E; ++e) d[e] = -g[e];
       } else {
@@ -196,48 +172,16 @@ __global__ __launch_bounds__(64) void first_order_kernel(const SolveArgs a, cons
         f = obj.template eval<W, E>(x, g, n, sl);   // StateType(function, x): the rebuild, run
       }
     }
-    nfev += trials + 1;                                    // the trials, and StateType(function, x) (solver.h:213-214)
-    trials_total += trials;
+    prog.nfev += trials + 1;                                  // the trials, and StateType(function, x) (solver.h:213-214)
+    prog.sum_k += trials;
 #pragma unroll
     for (int e = 0; e < E; ++e) x[e] = (sl * E + e < n) ? x[e] : 0.0;   // (a NaN step times 0 on a padding coordinate)
 
-    // ========================== Progress::Update ============================
-    num_iterations++;                                      // :188
-    f_delta = __builtin_fabs(f - fprev);                   // :189
-    double dx[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) dx[e] = x[e] - xprev[e];
-    x_delta = seg_amax<W, E>(dx);                          // :190
-    gradient_norm = seg_amax<W, E>(g);                     // :195
-    xinf_bound = (xinf_bound + x_delta) * (1.0 + 4.0 * eps);
-    status = progress_stop_tests<W, E>(a.stop, a.stop.num_iterations, a.stop.gradient_norm, num_iterations, f, fprev,
-                                       x_delta, f_delta, gradient_norm, xinf_bound, x, x_delta_violations,
-                                       f_delta_violations, past_f, past_init, past_pos, sl);
-    trace_iteration<E>(a, prob, n, sl, num_iterations, status, f, x_delta, f_delta, gradient_norm, x, g);
-    if (status != MI355_STATUS_CONTINUE) {
-      // ---- results of this problem (solver.h:223) ---------------------------
-#pragma unroll
-      for (int e = 0; e < E; ++e) {
-        const int j = sl * E + e;
-        if (j < n) {
-          a.x_out[prob * n + j] = canonical_nan(x[e]);
-          if (a.g_out) a.g_out[prob * n + j] = canonical_nan(g[e]);
-        }
-      }
-      if (sl == 0) {
-        a.f_out[prob] = canonical_nan(f);
-        if (a.progress_out) {
-          mi355_lbfgs_progress pr;
-          pr.status = status;
-          pr.num_iterations = num_iterations;
-          pr.nfev = nfev;
-          pr.sum_k = trials_total;
-          pr.x_delta = canonical_nan(x_delta);
-          pr.f_delta = canonical_nan(f_delta);
-          pr.gradient_norm = canonical_nan(gradient_norm);
-          a.progress_out[prob] = pr;
-        }
-      }
+    prog.update<W, E>(a.stop, a.stop.gradient_norm, true, f, fprev, x, xprev, g, past_f, sl);   // Progress::Update
+    trace_iteration<E>(a, prob, n, sl, prog.num_iterations, prog.status, f, prog.x_delta, prog.f_delta,
+                       prog.gradient_norm, x, g);
+    if (prog.status != MI355_STATUS_CONTINUE) {
+      prog.store<E>(a, prob, n, sl, f, x, g, true);   // (every NaN as the canonical one: "NaN results" above)
       need_fetch = true;
     }
   }

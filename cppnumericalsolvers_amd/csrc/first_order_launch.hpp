@@ -1,43 +1,16 @@
 // first_order_launch.hpp — launch of the first-order kernel (first_order_kernel.hpp) for one functor type, shared by
-// dispatch_first_order.hip (built-in objectives) and the units _build.py generates for user functors.
+// dispatch_first_order.hip (built-in objectives) and the units _build.py generates for user functors: the pre-check here,
+// the persistent-grid launch in solver_launch.hpp (no dynamic LDS).
 #pragma once
-#include "engine_internal.hpp"
 #include "first_order_kernel.hpp"
+#include "solver_launch.hpp"
 
 namespace mi355 {
 
 template <int W, int E, int Method, class Obj>
-int launch_first_order(mi355_lbfgs_ctx* ctx, SolveArgs args, const FirstOrderDeviceConfig& cfg, hipStream_t stream) {
-  constexpr int kSegs = kWave / W;
+int launch_first_order(mi355_lbfgs_ctx* ctx, const SolveArgs& args, const FirstOrderDeviceConfig& cfg, hipStream_t stream) {
   if (args.n > W * E) return fail(MI355_ERR_INVALID_ARGUMENT, "first-order solver: the lane mapping must cover n");
-  auto kern = first_order_kernel<W, E, Method, Obj>;
-  int per_cu = 0;
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kWave, 0));
-  if (per_cu < 1) per_cu = 1;
-  const long long blocks_needed = (args.B + kSegs - 1) / kSegs;
-  long long blocks_ll = static_cast<long long>(per_cu) * ctx->num_cus;
-  if (ctx->debug_blocks >= 1 && ctx->debug_blocks < blocks_ll) blocks_ll = ctx->debug_blocks;
-  if (blocks_ll > blocks_needed) blocks_ll = blocks_needed;
-  // plateau rings: MAX_PAST doubles per resident segment (the context's scratch is sized for the fullest grid)
-  if (static_cast<size_t>(blocks_ll) * kSegs * MI355_LBFGS_MAX_PAST > ctx->scratch_cap)
-    return fail(MI355_ERR_INVALID_ARGUMENT, "resident grid larger than the context's plateau-ring scratch");
-  args.scratch = ctx->scratch_dev;
-  args.next_problem = ctx->queue_dev;
-  HIP_TRY(hipMemsetAsync(ctx->queue_dev, 0, kQueueWords * sizeof(unsigned long long), stream));
-  HIP_TRY(hipEventRecord(ctx->ev_start, stream));
-  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks_ll)), dim3(kWave), 0, stream, args, cfg);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ctx->ev_stop, stream));
-  ctx->timed = true;
-  ctx->last_W = W;
-  ctx->last_E = E;
-  ctx->last_blocks = static_cast<int>(blocks_ll);
-  ctx->last_threads = kWave;
-  ctx->last_lds = 0;
-  ctx->last_mr = 0;
-  ctx->last_variant = MI355_KERNEL_GENERAL;
-  ctx->last_arith = MI355_ARITH_EXACT;
-  return MI355_OK;
+  return launch_persistent_solver<W, E>(ctx, first_order_kernel<W, E, Method, Obj>, 0, args, cfg, stream);
 }
 
 // The six built mappings: 8, 16, 32, 64 lanes at one coordinate per lane, 64 lanes at two and four.  ObjOf<W, E>::type

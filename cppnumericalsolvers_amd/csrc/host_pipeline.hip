@@ -934,100 +934,82 @@ int mi355_lbfgsb_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_des
 
 }  // extern "C"
 
+// ---- host-pointer entry points of TrustRegionNewton, NelderMead, NewtonDescent and the first-order solvers ----------
+namespace {
+const char kNRange[] = "n out of range [1, MI355_LBFGS_MAX_N]";
+
+// device(desc, B, x0, x_out, f_out, g_out, progress_out, stream): the solver's device entry point with its config bound.
+// n_max, n_message: the wrapper's own bound on n and the text of its refusal.  large_n_to_device: n > n_max is handed to
+// the device entry point instead (with B = 0), which words that refusal itself; n < 1 is still refused here.
+template <class Device>
+int solver_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const double* x0,
+                               double* x_out, double* f_out, double* g_out, mi355_lbfgs_progress* progress_out, int n_max,
+                               const char* n_message, bool large_n_to_device, Device device) {
+  if (!ctx || !desc) return fail(MI355_ERR_INVALID_ARGUMENT, "null context / desc");
+  if (B < 0) return fail(MI355_ERR_INVALID_ARGUMENT, "negative batch size");
+  if (B == 0) return device(desc, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
+  if (desc->n > n_max && large_n_to_device)
+    return device(desc, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (desc->n < 1 || desc->n > n_max) return fail(MI355_ERR_INVALID_ARGUMENT, n_message);
+  MI355_ENTER_DEVICE(ctx);
+  return run_host_batch(ctx, desc, B, x0, x_out, f_out, g_out, progress_out,
+                        [&](const mi355_lbfgs_desc* dd, int64_t bc, const double* a, double* b, double* f, double* gg,
+                            mi355_lbfgs_progress* p, hipStream_t st) { return device(dd, bc, a, b, f, gg, p, st); });
+}
+}  // namespace
+
 extern "C" int mi355_trust_region_newton_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
                                                              const mi355_trust_region_config* config, int64_t B,
                                                              const double* x0, double* x_out, double* f_out,
                                                              double* g_out, mi355_lbfgs_progress* progress_out) {
-  if (!ctx || !desc) return fail(MI355_ERR_INVALID_ARGUMENT, "null context / desc");
-  if (B < 0) return fail(MI355_ERR_INVALID_ARGUMENT, "negative batch size");
-  if (B == 0)
-    return mi355_trust_region_newton_minimize_batch(ctx, desc, config, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                    nullptr);
-  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
-  if (desc->n < 1 || desc->n > MI355_LBFGS_MAX_N) return fail(MI355_ERR_INVALID_ARGUMENT, "n out of range [1, MI355_LBFGS_MAX_N]");
-  MI355_ENTER_DEVICE(ctx);
-  return run_host_batch(ctx, desc, B, x0, x_out, f_out, g_out, progress_out,
-                        [&](const mi355_lbfgs_desc* dd, int64_t bc, const double* a, double* b, double* f, double* gg,
-                            mi355_lbfgs_progress* p, hipStream_t st) {
-                          return mi355_trust_region_newton_minimize_batch(ctx, dd, config, bc, a, b, f, gg, p, st);
-                        });
+  return solver_minimize_batch_host(ctx, desc, B, x0, x_out, f_out, g_out, progress_out, MI355_LBFGS_MAX_N, kNRange,
+                                    /*large_n_to_device=*/false,
+                                    [&](const mi355_lbfgs_desc* dd, auto... rest) {
+                                      return mi355_trust_region_newton_minimize_batch(ctx, dd, config, rest...);
+                                    });
 }
 
 extern "C" int mi355_nelder_mead_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
                                                      const mi355_nelder_mead_config* config, int64_t B,
                                                      const double* x0, double* x_out, double* f_out, double* g_out,
                                                      mi355_lbfgs_progress* progress_out) {
-  if (!ctx || !desc) return fail(MI355_ERR_INVALID_ARGUMENT, "null context / desc");
-  if (B < 0) return fail(MI355_ERR_INVALID_ARGUMENT, "negative batch size");
-  if (B == 0)
-    return mi355_nelder_mead_minimize_batch(ctx, desc, config, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
-  if (desc->n < 1 || desc->n > 64)
-    return fail(MI355_ERR_INVALID_ARGUMENT, "NelderMead is built for n <= 64 (the simplex is n x (n + 1) in LDS per problem)");
-  MI355_ENTER_DEVICE(ctx);
-  return run_host_batch(ctx, desc, B, x0, x_out, f_out, g_out, progress_out,
-                        [&](const mi355_lbfgs_desc* dd, int64_t bc, const double* a, double* b, double* f, double* gg,
-                            mi355_lbfgs_progress* p, hipStream_t st) {
-                          return mi355_nelder_mead_minimize_batch(ctx, dd, config, bc, a, b, f, gg, p, st);
-                        });
+  return solver_minimize_batch_host(ctx, desc, B, x0, x_out, f_out, g_out, progress_out, 64,
+                                    "NelderMead is built for n <= 64 (the simplex is n x (n + 1) in LDS per problem)",
+                                    /*large_n_to_device=*/false,
+                                    [&](const mi355_lbfgs_desc* dd, auto... rest) {
+                                      return mi355_nelder_mead_minimize_batch(ctx, dd, config, rest...);
+                                    });
 }
 
 extern "C" int mi355_newton_descent_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
                                                         const mi355_newton_descent_config* config, int64_t B,
                                                         const double* x0, double* x_out, double* f_out, double* g_out,
                                                         mi355_lbfgs_progress* progress_out) {
-  if (!ctx || !desc) return fail(MI355_ERR_INVALID_ARGUMENT, "null context / desc");
-  if (B < 0) return fail(MI355_ERR_INVALID_ARGUMENT, "negative batch size");
-  if (B == 0)
-    return mi355_newton_descent_minimize_batch(ctx, desc, config, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                               nullptr);
-  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
-  if (desc->n < 1 || desc->n > MI355_LBFGS_MAX_N) return fail(MI355_ERR_INVALID_ARGUMENT, "n out of range [1, MI355_LBFGS_MAX_N]");
-  MI355_ENTER_DEVICE(ctx);
-  return run_host_batch(ctx, desc, B, x0, x_out, f_out, g_out, progress_out,
-                        [&](const mi355_lbfgs_desc* dd, int64_t bc, const double* a, double* b, double* f, double* gg,
-                            mi355_lbfgs_progress* p, hipStream_t st) {
-                          return mi355_newton_descent_minimize_batch(ctx, dd, config, bc, a, b, f, gg, p, st);
-                        });
+  return solver_minimize_batch_host(ctx, desc, B, x0, x_out, f_out, g_out, progress_out, MI355_LBFGS_MAX_N, kNRange,
+                                    /*large_n_to_device=*/false,
+                                    [&](const mi355_lbfgs_desc* dd, auto... rest) {
+                                      return mi355_newton_descent_minimize_batch(ctx, dd, config, rest...);
+                                    });
 }
 
 extern "C" int mi355_gradient_descent_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B,
                                                           const double* x0, double* x_out, double* f_out, double* g_out,
                                                           mi355_lbfgs_progress* progress_out) {
-  if (!ctx || !desc) return fail(MI355_ERR_INVALID_ARGUMENT, "null context / desc");
-  if (B < 0) return fail(MI355_ERR_INVALID_ARGUMENT, "negative batch size");
-  if (B == 0)
-    return mi355_gradient_descent_minimize_batch(ctx, desc, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
-  if (desc->n > MI355_LBFGS_MAX_N)   // (the device entry point words the refusal)
-    return mi355_gradient_descent_minimize_batch(ctx, desc, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  if (desc->n < 1) return fail(MI355_ERR_INVALID_ARGUMENT, "n out of range [1, MI355_LBFGS_MAX_N]");
-  MI355_ENTER_DEVICE(ctx);
-  return run_host_batch(ctx, desc, B, x0, x_out, f_out, g_out, progress_out,
-                        [&](const mi355_lbfgs_desc* dd, int64_t bc, const double* a, double* b, double* f, double* gg,
-                            mi355_lbfgs_progress* p, hipStream_t st) {
-                          return mi355_gradient_descent_minimize_batch(ctx, dd, bc, a, b, f, gg, p, st);
-                        });
+  return solver_minimize_batch_host(ctx, desc, B, x0, x_out, f_out, g_out, progress_out, MI355_LBFGS_MAX_N, kNRange,
+                                    /*large_n_to_device=*/true,
+                                    [&](const mi355_lbfgs_desc* dd, auto... rest) {
+                                      return mi355_gradient_descent_minimize_batch(ctx, dd, rest...);
+                                    });
 }
 
 extern "C" int mi355_conjugated_gradient_descent_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
                                                                      const mi355_armijo_config* config, int64_t B,
                                                                      const double* x0, double* x_out, double* f_out,
                                                                      double* g_out, mi355_lbfgs_progress* progress_out) {
-  if (!ctx || !desc) return fail(MI355_ERR_INVALID_ARGUMENT, "null context / desc");
-  if (B < 0) return fail(MI355_ERR_INVALID_ARGUMENT, "negative batch size");
-  if (B == 0)
-    return mi355_conjugated_gradient_descent_minimize_batch(ctx, desc, config, 0, nullptr, nullptr, nullptr, nullptr,
-                                                            nullptr, nullptr);
-  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
-  if (desc->n > MI355_LBFGS_MAX_N)   // (the device entry point words the refusal)
-    return mi355_conjugated_gradient_descent_minimize_batch(ctx, desc, config, 0, nullptr, nullptr, nullptr, nullptr,
-                                                            nullptr, nullptr);
-  if (desc->n < 1) return fail(MI355_ERR_INVALID_ARGUMENT, "n out of range [1, MI355_LBFGS_MAX_N]");
-  MI355_ENTER_DEVICE(ctx);
-  return run_host_batch(ctx, desc, B, x0, x_out, f_out, g_out, progress_out,
-                        [&](const mi355_lbfgs_desc* dd, int64_t bc, const double* a, double* b, double* f, double* gg,
-                            mi355_lbfgs_progress* p, hipStream_t st) {
-                          return mi355_conjugated_gradient_descent_minimize_batch(ctx, dd, config, bc, a, b, f, gg, p, st);
-                        });
+  return solver_minimize_batch_host(ctx, desc, B, x0, x_out, f_out, g_out, progress_out, MI355_LBFGS_MAX_N, kNRange,
+                                    /*large_n_to_device=*/true,
+                                    [&](const mi355_lbfgs_desc* dd, auto... rest) {
+                                      return mi355_conjugated_gradient_descent_minimize_batch(ctx, dd, config, rest...);
+                                    });
 }

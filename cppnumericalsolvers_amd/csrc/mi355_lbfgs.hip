@@ -55,115 +55,53 @@ void register_user_objective(int objective_id, int W, UserDispatchFn fn, const c
   u.name = name ? name : "";
   user_table().emplace_back(objective_id, u);
 }
-void register_user_lbfgsb(int objective_id, UserLbfgsbFn fn) {
-  if (objective_id < MI355_OBJ_USER_FIRST) return;
-  for (auto& e : user_table()) {
-    if (e.first == objective_id) {
-      e.second.lbfgsb = fn;
-      return;
-    }
-  }
-  UserEntry u;
-  u.lbfgsb = fn;
-  user_table().emplace_back(objective_id, u);
-}
-void register_user_trust_region(int objective_id, UserTrustRegionFn fn) {
-  if (objective_id < MI355_OBJ_USER_FIRST) return;
-  for (auto& e : user_table()) {
-    if (e.first == objective_id) {
-      e.second.trust_region = fn;
-      return;
-    }
-  }
-  UserEntry u;
-  u.trust_region = fn;
-  user_table().emplace_back(objective_id, u);
-}
-UserTrustRegionFn user_trust_region(int objective_id) {
-  for (auto& e : user_table())
-    if (e.first == objective_id) return e.second.trust_region;
-  return nullptr;
-}
-void register_user_nelder_mead(int objective_id, UserNelderMeadFn fn) {
-  if (objective_id < MI355_OBJ_USER_FIRST) return;
-  for (auto& e : user_table()) {
-    if (e.first == objective_id) {
-      e.second.nelder_mead = fn;
-      return;
-    }
-  }
-  UserEntry u;
-  u.nelder_mead = fn;
-  user_table().emplace_back(objective_id, u);
-}
-UserNelderMeadFn user_nelder_mead(int objective_id) {
-  for (auto& e : user_table())
-    if (e.first == objective_id) return e.second.nelder_mead;
-  return nullptr;
-}
-void register_user_newton_descent(int objective_id, UserNewtonDescentFn fn) {
-  if (objective_id < MI355_OBJ_USER_FIRST) return;
-  for (auto& e : user_table()) {
-    if (e.first == objective_id) {
-      e.second.newton_descent = fn;
-      return;
-    }
-  }
-  UserEntry u;
-  u.newton_descent = fn;
-  user_table().emplace_back(objective_id, u);
-}
-UserNewtonDescentFn user_newton_descent(int objective_id) {
-  for (auto& e : user_table())
-    if (e.first == objective_id) return e.second.newton_descent;
-  return nullptr;
-}
-void register_user_first_order(int objective_id, UserFirstOrderFn fn) {
-  if (objective_id < MI355_OBJ_USER_FIRST) return;
-  for (auto& e : user_table()) {
-    if (e.first == objective_id) {
-      e.second.first_order = fn;
-      return;
-    }
-  }
-  UserEntry u;
-  u.first_order = fn;
-  user_table().emplace_back(objective_id, u);
-}
-UserFirstOrderFn user_first_order(int objective_id) {
-  for (auto& e : user_table())
-    if (e.first == objective_id) return e.second.first_order;
-  return nullptr;
-}
-void register_user_derivatives(int objective_id, UserDerivativesFn fn, int capabilities) {
-  if (objective_id < MI355_OBJ_USER_FIRST) return;
-  for (auto& e : user_table()) {
-    if (e.first == objective_id) {
-      e.second.derivatives = fn;
-      e.second.derivatives_capabilities = capabilities;
-      return;
-    }
-  }
-  UserEntry u;
-  u.derivatives = fn;
-  u.derivatives_capabilities = capabilities;
-  user_table().emplace_back(objective_id, u);
-}
-UserDerivativesFn user_derivatives(int objective_id) {
-  for (auto& e : user_table())
-    if (e.first == objective_id) return e.second.derivatives;
-  return nullptr;
-}
-int user_derivatives_capabilities(int objective_id) {
-  for (auto& e : user_table())
-    if (e.first == objective_id) return e.second.derivatives_capabilities;
-  return 0;
-}
-static const UserEntry* find_user_objective(int objective_id) {
+namespace {
+UserEntry* find_user_objective(int objective_id) {
   for (auto& e : user_table())
     if (e.first == objective_id) return &e.second;
   return nullptr;
 }
+// the entry a solver's generated unit registers into, made on first use; null for an id below MI355_OBJ_USER_FIRST
+UserEntry* user_entry(int objective_id) {
+  if (objective_id < MI355_OBJ_USER_FIRST) return nullptr;
+  if (UserEntry* u = find_user_objective(objective_id)) return u;
+  user_table().emplace_back(objective_id, UserEntry());
+  return &user_table().back().second;
+}
+// what a registered entry holds in `member`, or `none`
+template <class T>
+T user_lookup(int objective_id, T UserEntry::*member, T none) {
+  const UserEntry* u = find_user_objective(objective_id);
+  return u ? u->*member : none;
+}
+}  // namespace
+void register_user_lbfgsb(int objective_id, UserLbfgsbFn fn) {
+  if (UserEntry* u = user_entry(objective_id)) u->lbfgsb = fn;
+}
+void register_user_trust_region(int objective_id, UserTrustRegionFn fn) {
+  if (UserEntry* u = user_entry(objective_id)) u->trust_region = fn;
+}
+UserTrustRegionFn user_trust_region(int id) { return user_lookup<UserTrustRegionFn>(id, &UserEntry::trust_region, nullptr); }
+void register_user_nelder_mead(int objective_id, UserNelderMeadFn fn) {
+  if (UserEntry* u = user_entry(objective_id)) u->nelder_mead = fn;
+}
+UserNelderMeadFn user_nelder_mead(int id) { return user_lookup<UserNelderMeadFn>(id, &UserEntry::nelder_mead, nullptr); }
+void register_user_newton_descent(int objective_id, UserNewtonDescentFn fn) {
+  if (UserEntry* u = user_entry(objective_id)) u->newton_descent = fn;
+}
+UserNewtonDescentFn user_newton_descent(int id) { return user_lookup<UserNewtonDescentFn>(id, &UserEntry::newton_descent, nullptr); }
+void register_user_first_order(int objective_id, UserFirstOrderFn fn) {
+  if (UserEntry* u = user_entry(objective_id)) u->first_order = fn;
+}
+UserFirstOrderFn user_first_order(int id) { return user_lookup<UserFirstOrderFn>(id, &UserEntry::first_order, nullptr); }
+void register_user_derivatives(int objective_id, UserDerivativesFn fn, int capabilities) {
+  if (UserEntry* u = user_entry(objective_id)) {
+    u->derivatives = fn;
+    u->derivatives_capabilities = capabilities;
+  }
+}
+UserDerivativesFn user_derivatives(int id) { return user_lookup<UserDerivativesFn>(id, &UserEntry::derivatives, nullptr); }
+int user_derivatives_capabilities(int id) { return user_lookup<int>(id, &UserEntry::derivatives_capabilities, 0); }
 }  // namespace mi355
 
 namespace {
@@ -1295,6 +1233,42 @@ int mi355_lbfgs_selftest(mi355_lbfgs_ctx* ctx, int32_t* lane_maps, const double*
 
 }  // extern "C"
 
+// ---- shared by the entry points of TrustRegionNewton, NelderMead, NewtonDescent and the first-order solvers -----------
+namespace {
+// lanes per problem of a one-coordinate-per-lane solver (n <= 64): the padded width of n where the caller leaves it to the
+// library (0), else the caller's, which must be one of 8 / 16 / 32 / 64 and cover n; 0: it is not
+int lanes_covering(int requested, int n) {
+  if (requested == 0) {
+    int W = 8;
+    while (W < n) W <<= 1;
+    return W;
+  }
+  const bool built = requested == 8 || requested == 16 || requested == 32 || requested == 64;
+  return (built && requested >= n) ? requested : 0;
+}
+
+// the kernel arguments every one of these solvers fills the same way (m means nothing to them; the parameter blob is
+// the one upload_params left in the context)
+SolveArgs solver_args(const mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc& desc, int64_t B, const double* x0, double* x_out,
+                      double* f_out, double* g_out, mi355_lbfgs_progress* progress_out) {
+  SolveArgs args;
+  std::memset(&args, 0, sizeof(args));
+  args.x0 = x0;
+  args.x_out = x_out;
+  args.f_out = f_out;
+  args.g_out = g_out;
+  args.progress_out = progress_out;
+  args.obj_params = ctx->params_dev;
+  args.per_problem = desc.per_problem_data;
+  args.per_problem_stride = desc.per_problem_stride;
+  args.B = B;
+  args.n = desc.n;
+  args.m = 1;
+  args.stop = desc.stop;
+  return args;
+}
+}  // namespace
+
 // ---- TrustRegionNewton (trust_region_kernel.hpp) -------------------------------------------------------------------
 extern "C" int mi355_trust_region_default_config(mi355_trust_region_config* out) {
   if (!out) return fail(MI355_ERR_INVALID_ARGUMENT, "null config");
@@ -1342,13 +1316,9 @@ extern "C" int mi355_trust_region_newton_minimize_batch(mi355_lbfgs_ctx* ctx, co
                       "product records have none");
   if (desc.elems_per_lane != 0 && desc.elems_per_lane != 1)
     return fail(MI355_ERR_INVALID_ARGUMENT, "TrustRegionNewton: one coordinate per lane (elems_per_lane 0 or 1)");
-  int W = desc.lanes_per_problem;
-  if (W == 0) {
-    W = 8;
-    while (W < desc.n) W <<= 1;
-  } else if (!(W == 8 || W == 16 || W == 32 || W == 64) || W < desc.n) {
+  const int W = lanes_covering(desc.lanes_per_problem, desc.n);
+  if (W == 0)
     return fail(MI355_ERR_INVALID_ARGUMENT, "TrustRegionNewton: lanes_per_problem must be 8, 16, 32 or 64 and cover n");
-  }
   mi355_trust_region_config c;
   mi355_trust_region_default_config(&c);
   if (config) c = *config;
@@ -1370,20 +1340,7 @@ extern "C" int mi355_trust_region_newton_minimize_batch(mi355_lbfgs_ctx* ctx, co
   MI355_ENTER_DEVICE(ctx);
   rc = upload_params(ctx, &desc, W, 1, stream);
   if (rc != MI355_OK) return rc;
-  SolveArgs args;
-  std::memset(&args, 0, sizeof(args));
-  args.x0 = x0;
-  args.x_out = x_out;
-  args.f_out = f_out;
-  args.g_out = g_out;
-  args.progress_out = progress_out;
-  args.obj_params = ctx->params_dev;
-  args.per_problem = desc.per_problem_data;
-  args.per_problem_stride = desc.per_problem_stride;
-  args.B = B;
-  args.n = desc.n;
-  args.m = 1;
-  args.stop = desc.stop;
+  SolveArgs args = solver_args(ctx, desc, B, x0, x_out, f_out, g_out, progress_out);
   args.hess_from_functor = 1;
   args.hessian_condition_stop = desc.hessian_condition_stop;
   rc = setup_trace(ctx, &desc, B, stream, args);
@@ -1431,13 +1388,9 @@ extern "C" int mi355_nelder_mead_minimize_batch(mi355_lbfgs_ctx* ctx, const mi35
   if (rc != MI355_OK) return rc;
   if (desc.elems_per_lane != 0 && desc.elems_per_lane != 1)
     return fail(MI355_ERR_INVALID_ARGUMENT, "NelderMead: one coordinate per lane (elems_per_lane 0 or 1)");
-  int W = desc.lanes_per_problem;
-  if (W == 0) {
-    W = 8;
-    while (W < desc.n) W <<= 1;
-  } else if (!(W == 8 || W == 16 || W == 32 || W == 64) || W < desc.n) {
+  const int W = lanes_covering(desc.lanes_per_problem, desc.n);
+  if (W == 0)
     return fail(MI355_ERR_INVALID_ARGUMENT, "NelderMead: lanes_per_problem must be 8, 16, 32 or 64 and cover n");
-  }
   mi355_nelder_mead_config c;
   mi355_nelder_mead_default_config(&c);
   if (config) c = *config;
@@ -1456,20 +1409,7 @@ extern "C" int mi355_nelder_mead_minimize_batch(mi355_lbfgs_ctx* ctx, const mi35
   MI355_ENTER_DEVICE(ctx);
   rc = upload_params(ctx, &desc, W, 1, stream);
   if (rc != MI355_OK) return rc;
-  SolveArgs args;
-  std::memset(&args, 0, sizeof(args));
-  args.x0 = x0;
-  args.x_out = x_out;
-  args.f_out = f_out;
-  args.g_out = g_out;
-  args.progress_out = progress_out;
-  args.obj_params = ctx->params_dev;
-  args.per_problem = desc.per_problem_data;
-  args.per_problem_stride = desc.per_problem_stride;
-  args.B = B;
-  args.n = desc.n;
-  args.m = 1;
-  args.stop = desc.stop;
+  SolveArgs args = solver_args(ctx, desc, B, x0, x_out, f_out, g_out, progress_out);
   rc = setup_trace(ctx, &desc, B, stream, args);
   if (rc != MI355_OK) return rc;
   return dispatch_nelder_mead(ctx, W, desc.objective, args, dc, stream);
@@ -1514,16 +1454,12 @@ extern "C" int mi355_newton_descent_minimize_batch(mi355_lbfgs_ctx* ctx, const m
                       "product records have none");
   if (desc.elems_per_lane != 0 && desc.elems_per_lane != 1)
     return fail(MI355_ERR_INVALID_ARGUMENT, "NewtonDescent: one coordinate per lane (elems_per_lane 0 or 1)");
-  int W = desc.lanes_per_problem;
-  if (W == 0) {
-    // the padded width, except 16 < n <= 32: 64 lanes measured faster there (one problem per wavefront halves the LDS
-    // per wavefront; profiles/newton_descent_bench.jsonl)
-    W = 8;
-    while (W < desc.n) W <<= 1;
-    if (W == 32) W = 64;
-  } else if (!(W == 8 || W == 16 || W == 32 || W == 64) || W < desc.n) {
+  int W = lanes_covering(desc.lanes_per_problem, desc.n);
+  if (W == 0)
     return fail(MI355_ERR_INVALID_ARGUMENT, "NewtonDescent: lanes_per_problem must be 8, 16, 32 or 64 and cover n");
-  }
+  // the library's choice is the padded width, except 16 < n <= 32: 64 lanes measured faster there (one problem per
+  // wavefront halves the LDS per wavefront; profiles/newton_descent_bench.jsonl)
+  if (desc.lanes_per_problem == 0 && W == 32) W = 64;
   mi355_newton_descent_config c;
   mi355_newton_descent_default_config(&c);
   if (config) c = *config;
@@ -1537,20 +1473,7 @@ extern "C" int mi355_newton_descent_minimize_batch(mi355_lbfgs_ctx* ctx, const m
   MI355_ENTER_DEVICE(ctx);
   rc = upload_params(ctx, &desc, W, 1, stream);
   if (rc != MI355_OK) return rc;
-  SolveArgs args;
-  std::memset(&args, 0, sizeof(args));
-  args.x0 = x0;
-  args.x_out = x_out;
-  args.f_out = f_out;
-  args.g_out = g_out;
-  args.progress_out = progress_out;
-  args.obj_params = ctx->params_dev;
-  args.per_problem = desc.per_problem_data;
-  args.per_problem_stride = desc.per_problem_stride;
-  args.B = B;
-  args.n = desc.n;
-  args.m = 1;
-  args.stop = desc.stop;
+  SolveArgs args = solver_args(ctx, desc, B, x0, x_out, f_out, g_out, progress_out);
   args.hess_from_functor = 1;
   args.hessian_condition_stop = desc.hessian_condition_stop;
   rc = setup_trace(ctx, &desc, B, stream, args);
@@ -1642,20 +1565,7 @@ int first_order_minimize_batch(const char* solver, int method, mi355_lbfgs_ctx* 
   MI355_ENTER_DEVICE(ctx);
   rc = upload_params(ctx, &desc, W, E, stream);
   if (rc != MI355_OK) return rc;
-  SolveArgs args;
-  std::memset(&args, 0, sizeof(args));
-  args.x0 = x0;
-  args.x_out = x_out;
-  args.f_out = f_out;
-  args.g_out = g_out;
-  args.progress_out = progress_out;
-  args.obj_params = ctx->params_dev;
-  args.per_problem = desc.per_problem_data;
-  args.per_problem_stride = desc.per_problem_stride;
-  args.B = B;
-  args.n = desc.n;
-  args.m = 1;
-  args.stop = desc.stop;
+  SolveArgs args = solver_args(ctx, desc, B, x0, x_out, f_out, g_out, progress_out);
   rc = setup_trace(ctx, &desc, B, stream, args);
   if (rc != MI355_OK) return rc;
   return dispatch_first_order(ctx, method, W, E, desc.objective, args, dc, stream);

@@ -5,7 +5,7 @@
 //   NelderMead::OptimizationStep   solver/nelder_mead.h:102-195   (ordering, restart, centroid, the moves)
 //   makeInitialSimplex             :202-217
 //   isCoincident, shrink           :220-234
-//   Progress::Update               solver/progress.h:153-327      (progress_device.hpp)
+//   Progress::Update               solver/progress.h:153-327      (solver_driver.hpp, progress_device.hpp)
 //
 // Mapping.  A problem of dimension n <= W is owned by a segment of W consecutive lanes, one coordinate per lane (E = 1):
 // lane j keeps coordinate j of the returned iterate, of the centroid and of the trial points in registers.  In the
@@ -44,7 +44,7 @@
 #include "lbfgs_kernel.hpp"
 #include "nelder_mead_config.hpp"
 #include "objectives.hpp"
-#include "progress_device.hpp"
+#include "solver_driver.hpp"
 #include "wave_primitives.hpp"
 
 namespace mi355 {
@@ -63,8 +63,6 @@ __global__ __launch_bounds__(64) void nelder_mead_kernel(const SolveArgs a, cons
   static_assert(Obj::kLdsDoubles == 0 && Obj::shared_lds_doubles() == 0,
                 "the Nelder-Mead kernel is built for functors without LDS data");
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  constexpr int kSegs = kWave / W;
-  constexpr double eps = 2.220446049250313e-16;
 
   const int lane = threadIdx.x & (kWave - 1);
   const int seg = lane / W;
@@ -72,13 +70,11 @@ __global__ __launch_bounds__(64) void nelder_mead_kernel(const SolveArgs a, cons
   const int n = a.n;
   const int nv = n + 1;
   const bool own = sl < n;
-  const long long queue_length = a.count_dev ? static_cast<long long>(*a.count_dev) : a.B;
+  const long long queue_length = queue_length_of(a);
   double* const S = lds + seg * nelder_mead_lds_doubles(n, W);
   double* const fv = S + n * nv;
   int* const idx = reinterpret_cast<int*>(fv + nv);
-  // plateau ring of stop.past > 0: one MAX_PAST slot per resident segment in global scratch
-  double* const past_f =
-      a.scratch + (static_cast<size_t>(blockIdx.x) * kSegs + seg) * MI355_LBFGS_MAX_PAST;
+  double* const past_f = plateau_ring_slot<W>(a, seg);
   const double stop_gradient_norm = FIRST ? a.stop.gradient_norm : 0.0;
 
   Obj obj;
@@ -125,24 +121,15 @@ __global__ __launch_bounds__(64) void nelder_mead_kernel(const SolveArgs a, cons
 
   double x[1], g[1] = {0.0};
   double f = 0.0;
-  unsigned nfev = 0, num_iterations = 0;
-  int x_delta_violations = 0, f_delta_violations = 0, status = MI355_STATUS_NOT_STARTED;
-  double x_delta = 0.0, f_delta = 0.0, gradient_norm = 0.0, xinf_bound = 0.0;
-  bool past_init = false;
-  int past_pos = 0;
+  SolveProgress prog;                                      // prog.sum_k stays 0: this solver has no inner count
   long long prob = 0;
   bool need_fetch = true;
 
   while (true) {
     if (need_fetch) {
-      // ---- next unsolved problem from the queue ---------------------------------
-      unsigned long long nxt = 0;
-      if (sl == 0) nxt = atomicAdd(a.next_problem, 1ULL);
-      const unsigned lo = static_cast<unsigned>(seg_bcast_first<W>(static_cast<int>(nxt & 0xffffffffULL)));
-      const unsigned hi = static_cast<unsigned>(seg_bcast_first<W>(static_cast<int>(nxt >> 32)));
-      prob = static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo);
-      if (prob >= queue_length) break;
-      if (a.problem_map != nullptr) prob = a.problem_map[prob];
+      bool drained;
+      prob = fetch_problem<W>(a, queue_length, sl, drained);
+      if (drained) break;
       x[0] = own ? a.x0[prob * n + sl] : 0.0;
       obj.begin_problem(a.per_problem, prob, a.per_problem_stride, sl);
       need_fetch = false;
@@ -153,21 +140,14 @@ __global__ __launch_bounds__(64) void nelder_mead_kernel(const SolveArgs a, cons
       } else {
         f = obj.template value<W, 1>(x, n, sl);
       }
-      nfev = 1;
-      num_iterations = 0;
-      x_delta_violations = f_delta_violations = 0;
-      x_delta = f_delta = gradient_norm = 0.0;
-      status = MI355_STATUS_NOT_STARTED;
-      past_init = false;
-      past_pos = 0;
-      xinf_bound = seg_amax<W, 1>(x);
+      prog.reset<W, 1>(1, x);
       make_simplex(x[0]);
     }
 
     // ========================= NelderMead::OptimizationStep =========================
     const double fprev = f;
-    const double xprev = x[0];
-    nfev += static_cast<unsigned>(nv);                     // function(simplex.col(i)) for every vertex (:111-114)
+    const double xprev[1] = {x[0]};
+    prog.nfev += static_cast<unsigned>(nv);                     // function(simplex.col(i)) for every vertex (:111-114)
     rank_vertices();
     int best = idx[0];
     {
@@ -184,7 +164,7 @@ __global__ __launch_bounds__(64) void nelder_mead_kernel(const SolveArgs a, cons
       if (max_dist < cfg.degenerate_tol) {                 // restart around the best vertex (:130-139)
         const double xb = own ? S[sl + best * n] : 0.0;
         make_simplex(xb);
-        nfev += static_cast<unsigned>(nv);
+        prog.nfev += static_cast<unsigned>(nv);
         rank_vertices();
         best = idx[0];
       }
@@ -203,12 +183,12 @@ __global__ __launch_bounds__(64) void nelder_mead_kernel(const SolveArgs a, cons
     if (!shrink) {
       double xnew = xr, fnew = 0.0;
       const double f_r = value_of(xr);                     // :154
-      nfev += 1;
+      prog.nfev += 1;
       fnew = f_r;
       if (f_r < f_best) {                                  // expansion (:156-165)
         const double xe = (1.0 + cfg.rho * cfg.xi) * xbar - (cfg.rho * cfg.xi) * xw;
         const double f_e = value_of(xe);
-        nfev += 1;
+        prog.nfev += 1;
         if (f_e < f_r) {
           xnew = xe;
           fnew = f_e;
@@ -217,7 +197,7 @@ __global__ __launch_bounds__(64) void nelder_mead_kernel(const SolveArgs a, cons
       } else if (f_r < f_worst) {                          // outside contraction (:171-180)
         const double xc = (1.0 + cfg.rho * cfg.gamma) * xbar - (cfg.rho * cfg.gamma) * xw;
         const double f_c = value_of(xc);
-        nfev += 1;
+        prog.nfev += 1;
         if (f_c <= f_r) {
           xnew = xc;
           fnew = f_c;
@@ -227,7 +207,7 @@ __global__ __launch_bounds__(64) void nelder_mead_kernel(const SolveArgs a, cons
       } else {                                             // inside contraction (:181-190)
         const double xc = (1.0 - cfg.gamma) * xbar + cfg.gamma * xw;
         const double f_c = value_of(xc);
-        nfev += 1;
+        prog.nfev += 1;
         if (f_c < f_worst) {
           xnew = xc;
           fnew = f_c;
@@ -241,7 +221,7 @@ __global__ __launch_bounds__(64) void nelder_mead_kernel(const SolveArgs a, cons
       }
     }
     if (shrink) {                                          // :225-234: every vertex but the best moves towards it
-      nfev += static_cast<unsigned>(nv);
+      prog.nfev += static_cast<unsigned>(nv);
       const double xb = own ? S[sl + best * n] : 0.0;
       for (int i = 1; i < nv; ++i) {
         const int v = idx[i];
@@ -253,44 +233,19 @@ __global__ __launch_bounds__(64) void nelder_mead_kernel(const SolveArgs a, cons
     // the step returns the vertex that was best when the step ranked them (:194); Minimize rebuilds its state
     // (solver.h:210-216): the cached value in value mode, value and gradient in first mode
     x[0] = own ? S[sl + best * n] : 0.0;
-    nfev += 1;
+    prog.nfev += 1;
     if constexpr (FIRST) {
       f = obj.template eval<W, 1>(x, g, n, sl);
     } else {
       f = f_best;
     }
 
-    // ========================== Progress::Update ============================
-    num_iterations++;                                      // :188
-    f_delta = __builtin_fabs(f - fprev);                   // :189
-    double dx[1] = {x[0] - xprev};
-    x_delta = seg_amax<W, 1>(dx);                          // :190
-    if constexpr (FIRST) gradient_norm = seg_amax<W, 1>(g);  // :193-196
-    xinf_bound = (xinf_bound + x_delta) * (1.0 + 4.0 * eps);
-    status = progress_stop_tests<W, 1>(a.stop, a.stop.num_iterations, stop_gradient_norm, num_iterations, f, fprev,
-                                       x_delta, f_delta, gradient_norm, xinf_bound, x, x_delta_violations,
-                                       f_delta_violations, past_f, past_init, past_pos, sl);
-    trace_iteration<1>(a, prob, n, sl, num_iterations, status, f, x_delta, f_delta, gradient_norm, x, g);
-    if (status != MI355_STATUS_CONTINUE) {
-      // ---- results of this problem (solver.h:223) ---------------------------
-      if (own) {
-        a.x_out[prob * n + sl] = x[0];
-        if (a.g_out) a.g_out[prob * n + sl] = g[0];
-      }
-      if (sl == 0) {
-        a.f_out[prob] = f;
-        if (a.progress_out) {
-          mi355_lbfgs_progress pr;
-          pr.status = status;
-          pr.num_iterations = num_iterations;
-          pr.nfev = nfev;
-          pr.sum_k = 0;
-          pr.x_delta = x_delta;
-          pr.f_delta = f_delta;
-          pr.gradient_norm = gradient_norm;
-          a.progress_out[prob] = pr;
-        }
-      }
+    // Progress::Update: value mode forms no gradient, so gradient_norm stays 0 and the gradient test is off (:193-196)
+    prog.update<W, 1>(a.stop, stop_gradient_norm, FIRST, f, fprev, x, xprev, g, past_f, sl);
+    trace_iteration<1>(a, prob, n, sl, prog.num_iterations, prog.status, f, prog.x_delta, prog.f_delta,
+                       prog.gradient_norm, x, g);
+    if (prog.status != MI355_STATUS_CONTINUE) {
+      prog.store<1>(a, prob, n, sl, f, x, g, false);
       need_fetch = true;
     }
   }

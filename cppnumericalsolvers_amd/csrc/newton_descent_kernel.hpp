@@ -4,7 +4,7 @@
 //   Solver::Minimize                  solver/solver.h:181-224       (driver loop)
 //   NewtonDescent::OptimizationStep   solver/newton_descent.h:66-81 (H + 1e-5 I, LU solve, Armijo, x + rate d)
 //   Armijo<F, 2>::Search              linesearch/armijo.h:82-102    (the search with the Newton curvature term)
-//   Progress::Update                  solver/progress.h:153-327     (progress_device.hpp)
+//   Progress::Update                  solver/progress.h:153-327     (solver_driver.hpp, progress_device.hpp)
 //
 // Mapping.  As the trust-region kernel (trust_region_kernel.hpp): a problem of dimension n <= W is owned by a segment of
 // W consecutive lanes, one coordinate per lane; lane j keeps x_j, g_j, d_j in registers.  Per problem the segment's LDS
@@ -42,7 +42,7 @@
 #include "lu_device.hpp"
 #include "newton_descent_config.hpp"
 #include "objectives.hpp"
-#include "progress_device.hpp"
+#include "solver_driver.hpp"
 #include "wave_primitives.hpp"
 
 namespace mi355 {
@@ -59,8 +59,6 @@ __global__ __launch_bounds__(64) void newton_descent_kernel(const SolveArgs a, c
                 "the Newton-descent kernel is built for functors without LDS data");
   static_assert(HasHessFull<Obj>::value, "the Newton-descent kernel needs the functor's hess_full");
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  constexpr int kSegs = kWave / W;
-  constexpr double eps = 2.220446049250313e-16;
 
   const int lane = threadIdx.x & (kWave - 1);
   const int seg = lane / W;
@@ -68,59 +66,40 @@ __global__ __launch_bounds__(64) void newton_descent_kernel(const SolveArgs a, c
   const int n = a.n;
   const bool own = sl < n;
   const bool condition_on = a.hessian_condition_stop > 0.0;
-  const long long queue_length = a.count_dev ? static_cast<long long>(*a.count_dev) : a.B;
+  const long long queue_length = queue_length_of(a);
   const int lds_problem = newton_descent_lds_doubles(n, W, condition_on);
   double* const Hm = lds + seg * lds_problem;
   double* const Am = Hm + n * n;          // H + safe_guard I, then its LU
   double* const vbuf = Am + n * n;
   int* const piv = reinterpret_cast<int*>(vbuf + W);
   double* const hc = vbuf + W + lu_pivot_doubles(n);   // condition_hessian: a copy of H, the column buffers, pivots
-  // plateau ring of stop.past > 0: one MAX_PAST slot per resident segment in global scratch
-  double* const past_f =
-      a.scratch + (static_cast<size_t>(blockIdx.x) * kSegs + seg) * MI355_LBFGS_MAX_PAST;
+  double* const past_f = plateau_ring_slot<W>(a, seg);
 
   Obj obj;
   obj.load(a.obj_params, n, sl, nullptr, nullptr);
 
   double x[1], g[1], gt[1], xt[1];
   double f = 0.0;
-  unsigned nfev = 0, trials_total = 0, num_iterations = 0;
-  int x_delta_violations = 0, f_delta_violations = 0, status = MI355_STATUS_NOT_STARTED;
-  double x_delta = 0.0, f_delta = 0.0, gradient_norm = 0.0, xinf_bound = 0.0;
-  bool past_init = false;
-  int past_pos = 0;
+  SolveProgress prog;                                      // prog.sum_k: the trial evaluations
   long long prob = 0;
   bool need_fetch = true;
 
   while (true) {
     if (need_fetch) {
-      // ---- next unsolved problem from the queue ---------------------------------
-      unsigned long long nxt = 0;
-      if (sl == 0) nxt = atomicAdd(a.next_problem, 1ULL);
-      const unsigned lo = static_cast<unsigned>(seg_bcast_first<W>(static_cast<int>(nxt & 0xffffffffULL)));
-      const unsigned hi = static_cast<unsigned>(seg_bcast_first<W>(static_cast<int>(nxt >> 32)));
-      prob = static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo);
-      if (prob >= queue_length) break;
-      if (a.problem_map != nullptr) prob = a.problem_map[prob];
+      bool drained;
+      prob = fetch_problem<W>(a, queue_length, sl, drained);
+      if (drained) break;
       x[0] = own ? a.x0[prob * n + sl] : 0.0;
       obj.begin_problem(a.per_problem, prob, a.per_problem_stride, sl);
       need_fetch = false;
       // Solver::Minimize prologue (solver.h:189-192), Progress reset
       f = obj.template eval<W, 1>(x, g, n, sl);
-      nfev = 1;
-      trials_total = 0;
-      num_iterations = 0;
-      x_delta_violations = f_delta_violations = 0;
-      x_delta = f_delta = gradient_norm = 0.0;
-      status = MI355_STATUS_NOT_STARTED;
-      past_init = false;
-      past_pos = 0;
-      xinf_bound = seg_amax<W, 1>(x);
+      prog.reset<W, 1>(1, x);
       obj.template hess_full<W, 1>(x, Hm, n, sl);
     }
 
     // ======================= NewtonDescent::OptimizationStep ==========================
-    nfev += 1;                                             // function(current.x, &gradient, &hessian)   (:73)
+    prog.nfev += 1;                                           // function(current.x, &gradient, &hessian)   (:73)
     // hessian += safe_guard * Identity (:74): every element gets its (rounded) addend, the off-diagonal ones + 0.0
     for (int t = sl; t < n * n; t += W) Am[t] = Hm[t] + 0.0;
     segment_lds_fence();
@@ -130,7 +109,7 @@ __global__ __launch_bounds__(64) void newton_descent_kernel(const SolveArgs a, c
     double d = seg_lu_solve<W>(Am, piv, -g[0], n, sl);     // .solve(-gradient)
     d = own ? d : 0.0;
     // ---- Armijo<F, 2>::Search (armijo.h:82-102) ------------------------------------------
-    nfev += 1;                                             // f_in = function(x, &gradient, &hessian)   (:90)
+    prog.nfev += 1;                                           // f_in = function(x, &gradient, &hessian)   (:90)
     double alpha = 1.0;
     xt[0] = x[0] + alpha * d;
     double ft = obj.template eval<W, 1>(xt, gt, n, sl);    // function(x + alpha d)                     (:91)
@@ -148,7 +127,7 @@ __global__ __launch_bounds__(64) void newton_descent_kernel(const SolveArgs a, c
     segment_lds_fence();
     const double cache = cfg.armijo_c * gd + seg_sum<W>(v * d);   // (:92-95)
     const double fprev = f;
-    const double xprev = x[0];
+    const double xprev[1] = {x[0]};
     while (ft > fprev + alpha * cache) {                   // (:97-100)
       if (alpha * cfg.armijo_rho == alpha) break;          // the bounded search: see the head of this file
       alpha = alpha * cfg.armijo_rho;
@@ -156,52 +135,22 @@ __global__ __launch_bounds__(64) void newton_descent_kernel(const SolveArgs a, c
       ft = obj.template eval<W, 1>(xt, gt, n, sl);
       ++trials;
     }
-    nfev += trials + 1;                                    // the trials, and StateType(function, x + rate d) (solver.h)
-    trials_total += trials;
+    prog.nfev += trials + 1;                                  // the trials, and StateType(function, x + rate d) (solver.h)
+    prog.sum_k += trials;
     x[0] = xt[0];
     f = ft;
     g[0] = gt[0];
 
-    // ========================== Progress::Update ============================
-    num_iterations++;                                      // :188
-    f_delta = __builtin_fabs(f - fprev);                   // :189
-    double dx[1] = {x[0] - xprev};
-    x_delta = seg_amax<W, 1>(dx);                          // :190
-    gradient_norm = seg_amax<W, 1>(g);                     // :195
-    xinf_bound = (xinf_bound + x_delta) * (1.0 + 4.0 * eps);
-    status = progress_stop_tests<W, 1>(a.stop, a.stop.num_iterations, a.stop.gradient_norm, num_iterations, f, fprev,
-                                       x_delta, f_delta, gradient_norm, xinf_bound, x, x_delta_violations,
-                                       f_delta_violations, past_f, past_init, past_pos, sl);
+    prog.update<W, 1>(a.stop, a.stop.gradient_norm, true, f, fprev, x, xprev, g, past_f, sl);   // Progress::Update
     // H(x) of the new iterate: the condition test below and the next step
-    if (status == MI355_STATUS_CONTINUE) obj.template hess_full<W, 1>(x, Hm, n, sl);
-    if (condition_on && status == MI355_STATUS_CONTINUE) {  // :318-325, ||H|| ||H^-1|| at current_x (:203-210)
-      for (int t = sl; t < n * n; t += W) hc[t] = Hm[t];
-      segment_lds_fence();
-      const double condition =
-          seg_hessian_condition<W>(hc, hc + n * n, reinterpret_cast<int*>(hc + n * n + W * (n + 1)), n, sl);
-      if (condition > a.hessian_condition_stop) status = MI355_STATUS_HESSIAN_CONDITION_VIOLATION;
-    }
-    trace_iteration<1>(a, prob, n, sl, num_iterations, status, f, x_delta, f_delta, gradient_norm, x, g);
-    if (status != MI355_STATUS_CONTINUE) {
-      // ---- results of this problem (solver.h:223) ---------------------------
-      if (own) {
-        a.x_out[prob * n + sl] = x[0];
-        if (a.g_out) a.g_out[prob * n + sl] = g[0];
-      }
-      if (sl == 0) {
-        a.f_out[prob] = f;
-        if (a.progress_out) {
-          mi355_lbfgs_progress pr;
-          pr.status = status;
-          pr.num_iterations = num_iterations;
-          pr.nfev = nfev;
-          pr.sum_k = trials_total;
-          pr.x_delta = x_delta;
-          pr.f_delta = f_delta;
-          pr.gradient_norm = gradient_norm;
-          a.progress_out[prob] = pr;
-        }
-      }
+    if (prog.status == MI355_STATUS_CONTINUE) obj.template hess_full<W, 1>(x, Hm, n, sl);
+    if (condition_on && prog.status == MI355_STATUS_CONTINUE &&
+        hessian_condition_violated<W>(Hm, hc, n, sl, a.hessian_condition_stop))
+      prog.status = MI355_STATUS_HESSIAN_CONDITION_VIOLATION;
+    trace_iteration<1>(a, prob, n, sl, prog.num_iterations, prog.status, f, prog.x_delta, prog.f_delta,
+                       prog.gradient_norm, x, g);
+    if (prog.status != MI355_STATUS_CONTINUE) {
+      prog.store<1>(a, prob, n, sl, f, x, g, false);
       need_fetch = true;
     }
   }

@@ -1,9 +1,9 @@
 // progress_device.hpp — the stopping tests of Progress::Update (solver/progress.h:212-317) for one problem on its
-// segment, as a function for the solve kernels (trust_region_kernel.hpp).  The caller forms num_iterations, f_delta,
-// x_delta and gradient_norm (:188-195) and applies the condition_hessian test (:318-325) after this one, since how H is
-// obtained differs between the solvers.  lbfgs_kernel.hpp keeps its inline statement of the same tests: calling this
-// function from it compiled to the same arithmetic but changed the scalar-register spills of several of its kernels
-// (scripts/kernel_resources.py), whose budgets stay as they are.
+// segment, as a function for the solve kernels built on solver_driver.hpp, whose SolveProgress::update is the caller: it
+// forms num_iterations, f_delta, x_delta and gradient_norm (:188-195); the kernel applies the condition_hessian test
+// (:318-325) after it, since how H is obtained differs between the solvers.  lbfgs_kernel.hpp keeps its inline statement
+// of the same tests: calling this function from it compiled to the same arithmetic but changed the scalar-register
+// spills of several of its kernels (scripts/kernel_resources.py), whose budgets stay as they are.
 #pragma once
 #include "../../include/mi355_lbfgs.h"
 #include "more_thuente_device.hpp"

@@ -5,7 +5,7 @@
 //   TrustRegionNewton::OptimizationStep   solver/trust_region_newton.h:190-298 (model, rho, radius, rejection loop)
 //   SolveTrustRegionSubproblem            :339-426 (CG-Steihaug)
 //   ExtendStepToBoundary                  :436-451
-//   Progress::Update                      solver/progress.h:153-327 (progress_device.hpp)
+//   Progress::Update                      solver/progress.h:153-327 (solver_driver.hpp, progress_device.hpp)
 //
 // Mapping.  A problem of dimension n <= W is owned by a segment of W consecutive lanes, one coordinate per lane (E = 1):
 // lane j keeps x_j, g_j, and the CG vectors p_j, r_j, d_j in registers.  H(x) is n x n, column major, in the segment's
@@ -26,7 +26,7 @@
 #include "hessian_condition_device.hpp"
 #include "lbfgs_kernel.hpp"
 #include "objectives.hpp"
-#include "progress_device.hpp"
+#include "solver_driver.hpp"
 #include "trust_region_config.hpp"
 #include "wave_primitives.hpp"
 
@@ -43,8 +43,6 @@ __global__ __launch_bounds__(64) void trust_region_kernel(const SolveArgs a, con
                 "the trust-region kernel is built for functors without LDS data");
   static_assert(HasHessFull<Obj>::value, "the trust-region kernel needs the functor's hess_full");
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  constexpr int kSegs = kWave / W;
-  constexpr double eps = 2.220446049250313e-16;
   constexpr double kInf = __builtin_inf();
 
   const int lane = threadIdx.x & (kWave - 1);
@@ -53,14 +51,12 @@ __global__ __launch_bounds__(64) void trust_region_kernel(const SolveArgs a, con
   const int n = a.n;
   const bool own = sl < n;
   const bool condition_on = a.hessian_condition_stop > 0.0;
-  const long long queue_length = a.count_dev ? static_cast<long long>(*a.count_dev) : a.B;
+  const long long queue_length = queue_length_of(a);
   const int lds_problem = trust_region_lds_doubles(n, W, condition_on);
   double* const Hm = lds + seg * lds_problem;
   double* const vbuf = Hm + n * n;
   double* const hc = vbuf + W;            // condition_hessian: a copy of H, the LU's column buffers and pivots
-  // plateau ring of stop.past > 0: one MAX_PAST slot per resident segment in global scratch
-  double* const past_f =
-      a.scratch + (static_cast<size_t>(blockIdx.x) * kSegs + seg) * MI355_LBFGS_MAX_PAST;
+  double* const past_f = plateau_ring_slot<W>(a, seg);
 
   Obj obj;
   obj.load(a.obj_params, n, sl, nullptr, nullptr);
@@ -81,44 +77,27 @@ __global__ __launch_bounds__(64) void trust_region_kernel(const SolveArgs a, con
 
   double x[1], g[1], gt[1], xt[1];
   double f = 0.0, radius = 0.0;
-  unsigned nfev = 0, cg_total = 0, num_iterations = 0;
-  int x_delta_violations = 0, f_delta_violations = 0, status = MI355_STATUS_NOT_STARTED;
-  double x_delta = 0.0, f_delta = 0.0, gradient_norm = 0.0, xinf_bound = 0.0;
-  bool past_init = false;
-  int past_pos = 0;
+  SolveProgress prog;                                      // prog.sum_k: the CG iterations
   long long prob = 0;
   bool need_fetch = true;
 
   while (true) {
     if (need_fetch) {
-      // ---- next unsolved problem from the queue ---------------------------------
-      unsigned long long nxt = 0;
-      if (sl == 0) nxt = atomicAdd(a.next_problem, 1ULL);
-      const unsigned lo = static_cast<unsigned>(seg_bcast_first<W>(static_cast<int>(nxt & 0xffffffffULL)));
-      const unsigned hi = static_cast<unsigned>(seg_bcast_first<W>(static_cast<int>(nxt >> 32)));
-      prob = static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo);
-      if (prob >= queue_length) break;
-      if (a.problem_map != nullptr) prob = a.problem_map[prob];
+      bool drained;
+      prob = fetch_problem<W>(a, queue_length, sl, drained);
+      if (drained) break;
       x[0] = own ? a.x0[prob * n + sl] : 0.0;
       obj.begin_problem(a.per_problem, prob, a.per_problem_stride, sl);
       need_fetch = false;
       // Solver::Minimize prologue (solver.h:189-192), InitializeSolver (:180-187), Progress reset
       f = obj.template eval<W, 1>(x, g, n, sl);
-      nfev = 1;
-      cg_total = 0;
       radius = cfg.initial_radius;
-      num_iterations = 0;
-      x_delta_violations = f_delta_violations = 0;
-      x_delta = f_delta = gradient_norm = 0.0;
-      status = MI355_STATUS_NOT_STARTED;
-      past_init = false;
-      past_pos = 0;
-      xinf_bound = seg_amax<W, 1>(x);
+      prog.reset<W, 1>(1, x);
       obj.template hess_full<W, 1>(x, Hm, n, sl);
     }
 
     // ======================= TrustRegionNewton::OptimizationStep ======================
-    nfev += 1;                                             // function(current.x, &gradient, &hessian)   (:201)
+    prog.nfev += 1;                                           // function(current.x, &gradient, &hessian)   (:201)
     const double gnorm_inf = seg_amax<W, 1>(g);            // :213-214
     const double sq = __builtin_sqrt(gnorm_inf);
     const double forcing = (sq < 0.5) ? sq : 0.5;          // std::min(0.5, sqrt(.)) (:215-216)
@@ -127,7 +106,7 @@ __global__ __launch_bounds__(64) void trust_region_kernel(const SolveArgs a, con
     // it: the reference's CG cap is the floor alone, reproduced here
     const int cg_max = cfg.cg_extra_iterations;
     const double fprev = f;
-    const double xprev = x[0];
+    const double xprev[1] = {x[0]};
     bool accepted = false;
     for (int retry = 0; retry < cfg.rejection_retry_limit; ++retry) {
       // ---- CG-Steihaug (:339-426) ----------------------------------------------------
@@ -172,7 +151,7 @@ __global__ __launch_bounds__(64) void trust_region_kernel(const SolveArgs a, con
       // ---- agreement ratio (:260-280) -------------------------------------------------
       xt[0] = x[0] + p;
       const double trial_value = obj.template eval<W, 1>(xt, gt, n, sl);
-      nfev += 1;
+      prog.nfev += 1;
       const double hp = hess_times(p);
       const double predicted = -dot(g[0], p) - 0.5 * dot(p, hp);
       const double actual = fprev - trial_value;
@@ -185,12 +164,12 @@ __global__ __launch_bounds__(64) void trust_region_kernel(const SolveArgs a, con
         const double grown = cfg.expand_factor * radius;
         radius = (cfg.max_radius < grown) ? cfg.max_radius : grown;
       }
-      cg_total += cg_iters;
+      prog.sum_k += cg_iters;
       if (rho > cfg.acceptance_threshold) {                // :305-307: StateType(function, trial_x)
         x[0] = xt[0];
         f = trial_value;
         g[0] = gt[0];
-        nfev += 1;
+        prog.nfev += 1;
         accepted = true;
         break;
       }
@@ -199,52 +178,22 @@ __global__ __launch_bounds__(64) void trust_region_kernel(const SolveArgs a, con
         // rho is NaN or between rho_low and the acceptance threshold: the radius stayed put, so every remaining retry
         // solves the identical subproblem and rejects it again — what those retries would add is counted, not re-run
         const unsigned left = static_cast<unsigned>(cfg.rejection_retry_limit - retry - 1);
-        nfev += left;
-        cg_total += left * cg_iters;
+        prog.nfev += left;
+        prog.sum_k += left * cg_iters;
         break;
       }
     }
 
-    // ========================== Progress::Update ============================
-    num_iterations++;                                      // :188
-    f_delta = __builtin_fabs(f - fprev);                   // :189
-    double dx[1] = {x[0] - xprev};
-    x_delta = seg_amax<W, 1>(dx);                          // :190
-    gradient_norm = seg_amax<W, 1>(g);                     // :195
-    xinf_bound = (xinf_bound + x_delta) * (1.0 + 4.0 * eps);
-    status = progress_stop_tests<W, 1>(a.stop, a.stop.num_iterations, a.stop.gradient_norm, num_iterations, f, fprev,
-                                       x_delta, f_delta, gradient_norm, xinf_bound, x, x_delta_violations,
-                                       f_delta_violations, past_f, past_init, past_pos, sl);
+    prog.update<W, 1>(a.stop, a.stop.gradient_norm, true, f, fprev, x, xprev, g, past_f, sl);   // Progress::Update
     // H(x) of the new iterate (unchanged on a stalled step): the condition test below and the next step's model
-    if (accepted && status == MI355_STATUS_CONTINUE) obj.template hess_full<W, 1>(x, Hm, n, sl);
-    if (condition_on && status == MI355_STATUS_CONTINUE) {  // :318-325, ||H|| ||H^-1|| at current_x (:203-210)
-      for (int t = sl; t < n * n; t += W) hc[t] = Hm[t];
-      segment_lds_fence();
-      const double condition =
-          seg_hessian_condition<W>(hc, hc + n * n, reinterpret_cast<int*>(hc + n * n + W * (n + 1)), n, sl);
-      if (condition > a.hessian_condition_stop) status = MI355_STATUS_HESSIAN_CONDITION_VIOLATION;
-    }
-    trace_iteration<1>(a, prob, n, sl, num_iterations, status, f, x_delta, f_delta, gradient_norm, x, g);
-    if (status != MI355_STATUS_CONTINUE) {
-      // ---- results of this problem (solver.h:223) ---------------------------
-      if (own) {
-        a.x_out[prob * n + sl] = x[0];
-        if (a.g_out) a.g_out[prob * n + sl] = g[0];
-      }
-      if (sl == 0) {
-        a.f_out[prob] = f;
-        if (a.progress_out) {
-          mi355_lbfgs_progress pr;
-          pr.status = status;
-          pr.num_iterations = num_iterations;
-          pr.nfev = nfev;
-          pr.sum_k = cg_total;
-          pr.x_delta = x_delta;
-          pr.f_delta = f_delta;
-          pr.gradient_norm = gradient_norm;
-          a.progress_out[prob] = pr;
-        }
-      }
+    if (accepted && prog.status == MI355_STATUS_CONTINUE) obj.template hess_full<W, 1>(x, Hm, n, sl);
+    if (condition_on && prog.status == MI355_STATUS_CONTINUE &&
+        hessian_condition_violated<W>(Hm, hc, n, sl, a.hessian_condition_stop))
+      prog.status = MI355_STATUS_HESSIAN_CONDITION_VIOLATION;
+    trace_iteration<1>(a, prob, n, sl, prog.num_iterations, prog.status, f, prog.x_delta, prog.f_delta,
+                       prog.gradient_norm, x, g);
+    if (prog.status != MI355_STATUS_CONTINUE) {
+      prog.store<1>(a, prob, n, sl, f, x, g, false);
       need_fetch = true;
     }
   }

@@ -282,6 +282,10 @@ class BatchedLbfgs:
     def _stream(self):
         return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _config_args(self):
+        """What the solver's entry points take between the desc and B: nothing here, a config struct in _ConfiguredSolver."""
+        return ()
+
     # -- API ---------------------------------------------------------------
     def _on_device(self, t, what):
         """The C entry points dereference raw pointers on the context's device."""
@@ -323,7 +327,7 @@ class BatchedLbfgs:
             self._trace_keepalive = trace
             d.trace = trace.c_pointer()
         capi.check(getattr(self.ctx._lib, self._entry)(
-            self.ctx.handle, C.byref(d), B, x0.data_ptr(), x.data_ptr(), f.data_ptr(),
+            self.ctx.handle, C.byref(d), *self._config_args(), B, x0.data_ptr(), x.data_ptr(), f.data_ptr(),
             g.data_ptr() if g is not None else None, prog.data_ptr() if prog is not None else None,
             self._stream()))
         return x, f, g, prog
@@ -343,8 +347,8 @@ class BatchedLbfgs:
         prog = np.zeros(B, dtype=capi.PROGRESS_DTYPE)
         d = self._desc(objective, n, pp_ptr, pp_stride)
         capi.check(getattr(self.ctx._lib, self._entry + "_host")(
-            self.ctx.handle, C.byref(d), B, x0.ctypes.data, x.ctypes.data, f.ctypes.data, g.ctypes.data,
-            prog.ctypes.data))
+            self.ctx.handle, C.byref(d), *self._config_args(), B, x0.ctypes.data, x.ctypes.data, f.ctypes.data,
+            g.ctypes.data, prog.ctypes.data))
         return x, f, g, prog
 
     def evaluate(self, objective, x, per_problem=None):
@@ -427,7 +431,23 @@ class BatchedBfgs(BatchedLbfgs):
                          elems_per_lane=elems_per_lane)
 
 
-class BatchedTrustRegionNewton(BatchedLbfgs):
+class _ConfiguredSolver(BatchedLbfgs):
+    """What TrustRegionNewton, NewtonDescent, NelderMead and the two first-order solvers share on top of BatchedLbfgs: their
+    entry points (`_entry`, `_entry` + "_host") take the solver's config struct after the desc — `self.config`, or nothing
+    where the solver has none (GradientDescent) — and their host entry points take no per-problem data."""
+
+    def _config_args(self):
+        config = getattr(self, "config", None)
+        return () if config is None else (C.byref(config),)
+
+    def minimize_host(self, objective, x0, per_problem=None):
+        """Same through the host-pointer entry point (numpy in, numpy out, synchronous)."""
+        if per_problem is not None:
+            raise ValueError("per-problem data: use minimize() with device tensors")
+        return super().minimize_host(objective, x0)
+
+
+class BatchedTrustRegionNewton(_ConfiguredSolver):
     """Batched `TrustRegionNewton<F>` (reference solver/trust_region_newton.h): one Hessian per outer step, CG-Steihaug
     on the quadratic model, the agreement ratio, the radius update and the in-step rejection loop; n <= 64, objectives
     whose device functor has a hess_full (Rosenbrock, DiagQuadratic, user functors built with trust_region=True).
@@ -450,41 +470,6 @@ class BatchedTrustRegionNewton(BatchedLbfgs):
         d.hessian_condition_stop = self.condition_hessian
         return d
 
-    def minimize(self, objective, x0, want_gradient=True, want_progress=True, per_problem=None, trace=None):
-        torch = self._torch
-        if x0.dtype != torch.float64 or x0.dim() != 2 or not x0.is_cuda:
-            raise ValueError("x0 must be a [B, n] float64 CUDA tensor")
-        self._on_device(x0, "x0")
-        x0 = x0.contiguous()
-        B, n = x0.shape
-        x = torch.empty_like(x0)
-        f = torch.empty(B, dtype=torch.float64, device=x0.device)
-        g = torch.empty_like(x0) if want_gradient else None
-        prog = torch.empty(B * capi.PROGRESS_DTYPE.itemsize, dtype=torch.uint8, device=x0.device) \
-            if want_progress else None
-        d = self._desc(objective, n, *self._pp_device(per_problem, B))
-        if trace is not None:
-            self._trace_keepalive = trace
-            d.trace = trace.c_pointer()
-        capi.check(self.ctx._lib.mi355_trust_region_newton_minimize_batch(
-            self.ctx.handle, C.byref(d), C.byref(self.config), B, x0.data_ptr(), x.data_ptr(), f.data_ptr(),
-            g.data_ptr() if g is not None else None, prog.data_ptr() if prog is not None else None, self._stream()))
-        return x, f, g, prog
-
-    def minimize_host(self, objective, x0, per_problem=None):
-        """Same through the host-pointer entry point (numpy in, numpy out, synchronous)."""
-        if per_problem is not None:
-            raise ValueError("per-problem data: use minimize() with device tensors")
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        B, n = x0.shape
-        x, g, f = np.empty_like(x0), np.empty_like(x0), np.empty(B)
-        prog = np.zeros(B, dtype=capi.PROGRESS_DTYPE)
-        d = self._desc(objective, n)
-        capi.check(self.ctx._lib.mi355_trust_region_newton_minimize_batch_host(
-            self.ctx.handle, C.byref(d), C.byref(self.config), B, x0.ctypes.data, x.ctypes.data, f.ctypes.data,
-            g.ctypes.data, prog.ctypes.data))
-        return x, f, g, prog
-
 
 class BatchedNewtonDescent(BatchedTrustRegionNewton):
     """Batched `NewtonDescent<F>` (reference solver/newton_descent.h): per step d = (H + safe_guard I).lu().solve(-g) and
@@ -504,43 +489,8 @@ class BatchedNewtonDescent(BatchedTrustRegionNewton):
                               condition_hessian=condition_hessian)
         self.config = capi.default_newton_descent_config(**config)
 
-    def minimize(self, objective, x0, want_gradient=True, want_progress=True, per_problem=None, trace=None):
-        torch = self._torch
-        if x0.dtype != torch.float64 or x0.dim() != 2 or not x0.is_cuda:
-            raise ValueError("x0 must be a [B, n] float64 CUDA tensor")
-        self._on_device(x0, "x0")
-        x0 = x0.contiguous()
-        B, n = x0.shape
-        x = torch.empty_like(x0)
-        f = torch.empty(B, dtype=torch.float64, device=x0.device)
-        g = torch.empty_like(x0) if want_gradient else None
-        prog = torch.empty(B * capi.PROGRESS_DTYPE.itemsize, dtype=torch.uint8, device=x0.device) \
-            if want_progress else None
-        d = self._desc(objective, n, *self._pp_device(per_problem, B))
-        if trace is not None:
-            self._trace_keepalive = trace
-            d.trace = trace.c_pointer()
-        capi.check(self.ctx._lib.mi355_newton_descent_minimize_batch(
-            self.ctx.handle, C.byref(d), C.byref(self.config), B, x0.data_ptr(), x.data_ptr(), f.data_ptr(),
-            g.data_ptr() if g is not None else None, prog.data_ptr() if prog is not None else None, self._stream()))
-        return x, f, g, prog
 
-    def minimize_host(self, objective, x0, per_problem=None):
-        """Same through the host-pointer entry point (numpy in, numpy out, synchronous)."""
-        if per_problem is not None:
-            raise ValueError("per-problem data: use minimize() with device tensors")
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        B, n = x0.shape
-        x, g, f = np.empty_like(x0), np.empty_like(x0), np.empty(B)
-        prog = np.zeros(B, dtype=capi.PROGRESS_DTYPE)
-        d = self._desc(objective, n)
-        capi.check(self.ctx._lib.mi355_newton_descent_minimize_batch_host(
-            self.ctx.handle, C.byref(d), C.byref(self.config), B, x0.ctypes.data, x.ctypes.data, f.ctypes.data,
-            g.ctypes.data, prog.ctypes.data))
-        return x, f, g, prog
-
-
-class BatchedGradientDescent(BatchedLbfgs):
+class BatchedGradientDescent(_ConfiguredSolver):
     """Batched `GradientDescent<F>` (reference solver/gradient_descent.h with the More-Thuente search): per step the search
     runs along -g from alpha = 1 and the step is x - rate g; n <= 256, x and g in registers; Rosenbrock, DiagQuadratic
     and user functors built with first_order=True.  progress.sum_k holds the solve's total trial points."""
@@ -558,44 +508,6 @@ class BatchedGradientDescent(BatchedLbfgs):
         d.hessian_condition = 0.0
         d.hessian_condition_stop = 0.0
         return d
-
-    def _config_args(self):
-        return () if self._config is None else (C.byref(self._config),)
-
-    def minimize(self, objective, x0, want_gradient=True, want_progress=True, per_problem=None, trace=None):
-        torch = self._torch
-        if x0.dtype != torch.float64 or x0.dim() != 2 or not x0.is_cuda:
-            raise ValueError("x0 must be a [B, n] float64 CUDA tensor")
-        self._on_device(x0, "x0")
-        x0 = x0.contiguous()
-        B, n = x0.shape
-        x = torch.empty_like(x0)
-        f = torch.empty(B, dtype=torch.float64, device=x0.device)
-        g = torch.empty_like(x0) if want_gradient else None
-        prog = torch.empty(B * capi.PROGRESS_DTYPE.itemsize, dtype=torch.uint8, device=x0.device) \
-            if want_progress else None
-        d = self._desc(objective, n, *self._pp_device(per_problem, B))
-        if trace is not None:
-            self._trace_keepalive = trace
-            d.trace = trace.c_pointer()
-        capi.check(getattr(self.ctx._lib, self._entry)(
-            self.ctx.handle, C.byref(d), *self._config_args(), B, x0.data_ptr(), x.data_ptr(), f.data_ptr(),
-            g.data_ptr() if g is not None else None, prog.data_ptr() if prog is not None else None, self._stream()))
-        return x, f, g, prog
-
-    def minimize_host(self, objective, x0, per_problem=None):
-        """Same through the host-pointer entry point (numpy in, numpy out, synchronous)."""
-        if per_problem is not None:
-            raise ValueError("per-problem data: use minimize() with device tensors")
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        B, n = x0.shape
-        x, g, f = np.empty_like(x0), np.empty_like(x0), np.empty(B)
-        prog = np.zeros(B, dtype=capi.PROGRESS_DTYPE)
-        d = self._desc(objective, n)
-        capi.check(getattr(self.ctx._lib, self._entry + "_host")(
-            self.ctx.handle, C.byref(d), *self._config_args(), B, x0.ctypes.data, x.ctypes.data, f.ctypes.data,
-            g.ctypes.data, prog.ctypes.data))
-        return x, f, g, prog
 
 
 class BatchedConjugatedGradientDescent(BatchedGradientDescent):
@@ -618,7 +530,7 @@ class BatchedConjugatedGradientDescent(BatchedGradientDescent):
         return self._config
 
 
-class BatchedNelderMead(BatchedLbfgs):
+class BatchedNelderMead(_ConfiguredSolver):
     """Batched `NelderMead<F>` (reference solver/nelder_mead.h): the derivative-free simplex method, one problem per
     wavefront segment with the simplex and its vertex values in LDS; n <= 64, Rosenbrock, DiagQuadratic and user functors
     built with nelder_mead=True.
@@ -644,41 +556,6 @@ class BatchedNelderMead(BatchedLbfgs):
         d.hessian_condition = 0.0
         d.hessian_condition_stop = 0.0
         return d
-
-    def minimize(self, objective, x0, want_gradient=True, want_progress=True, per_problem=None, trace=None):
-        torch = self._torch
-        if x0.dtype != torch.float64 or x0.dim() != 2 or not x0.is_cuda:
-            raise ValueError("x0 must be a [B, n] float64 CUDA tensor")
-        self._on_device(x0, "x0")
-        x0 = x0.contiguous()
-        B, n = x0.shape
-        x = torch.empty_like(x0)
-        f = torch.empty(B, dtype=torch.float64, device=x0.device)
-        g = torch.empty_like(x0) if want_gradient else None
-        prog = torch.empty(B * capi.PROGRESS_DTYPE.itemsize, dtype=torch.uint8, device=x0.device) \
-            if want_progress else None
-        d = self._desc(objective, n, *self._pp_device(per_problem, B))
-        if trace is not None:
-            self._trace_keepalive = trace
-            d.trace = trace.c_pointer()
-        capi.check(self.ctx._lib.mi355_nelder_mead_minimize_batch(
-            self.ctx.handle, C.byref(d), C.byref(self.config), B, x0.data_ptr(), x.data_ptr(), f.data_ptr(),
-            g.data_ptr() if g is not None else None, prog.data_ptr() if prog is not None else None, self._stream()))
-        return x, f, g, prog
-
-    def minimize_host(self, objective, x0, per_problem=None):
-        """Same through the host-pointer entry point (numpy in, numpy out, synchronous)."""
-        if per_problem is not None:
-            raise ValueError("per-problem data: use minimize() with device tensors")
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        B, n = x0.shape
-        x, g, f = np.empty_like(x0), np.empty_like(x0), np.empty(B)
-        prog = np.zeros(B, dtype=capi.PROGRESS_DTYPE)
-        d = self._desc(objective, n)
-        capi.check(self.ctx._lib.mi355_nelder_mead_minimize_batch_host(
-            self.ctx.handle, C.byref(d), C.byref(self.config), B, x0.ctypes.data, x.ctypes.data, f.ctypes.data,
-            g.ctypes.data, prog.ctypes.data))
-        return x, f, g, prog
 
 
 class BatchedLbfgsb(BatchedLbfgs):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """TrustRegionNewton throughput on one MI355X (csrc/trust_region_kernel.hpp), with BatchedLbfgs on the same batch:
 65,536 x Rosenbrock-32 and 16,384 x Rosenbrock-64 from the bench's synthetic starts (amd.synthetic_x0_host), default
-stopping preset and config.  Per shape and lane mapping: kernel ms (median of --reps), solves/s, and the mean / max of
+stopping preset and config.  Per shape and lane mapping: kernel ms (median, min and max of --reps), solves/s, and the mean / max of
 iterations, nfev and CG iterations.  The mapping sweep covers every padded width: n = 8, 16, 32 at their own width and
 at the next ones, n = 64 at 64 (65,536 problems at n <= 32).  One JSON object per line (JSON lines) on stdout; --out also
 writes them to a file.
@@ -27,7 +27,7 @@ def run(solver, obj, x0, reps):
         x, f, g, p = solver.minimize(obj, x0)
         torch.cuda.synchronize()
         ms.append(solver.last_kernel_ms())
-    return float(np.median(ms)), amd.progress_to_numpy(p)
+    return ms, amd.progress_to_numpy(p)
 
 
 def main():
@@ -46,8 +46,10 @@ def main():
             runs.append(("lbfgs", 0, amd.BatchedLbfgs()))
         for name, lanes, solver in runs:
             run(solver, amd.Rosenbrock(), x0, 1)   # warm-up
-            ms, p = run(solver, amd.Rosenbrock(), x0, args.reps)
+            all_ms, p = run(solver, amd.Rosenbrock(), x0, args.reps)
+            ms = float(np.median(all_ms))
             row = dict(solver=name, B=B, n=n, lanes_per_problem=lanes or "auto", kernel_ms=round(ms, 3),
+                       kernel_ms_min=round(min(all_ms), 3), kernel_ms_max=round(max(all_ms), 3), reps=args.reps,
                        solves_per_s=round(B / (ms * 1e-3)), iterations_mean=round(float(p["num_iterations"].mean()), 2),
                        iterations_max=int(p["num_iterations"].max()), nfev_mean=round(float(p["nfev"].mean()), 2),
                        status_counts={int(s): int(c) for s, c in zip(*np.unique(p["status"], return_counts=True))})
