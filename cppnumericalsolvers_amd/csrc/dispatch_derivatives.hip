@@ -35,9 +35,8 @@ int derivative_capabilities_of(int objective) {
     case MI355_OBJ_ROSENBROCK: return derivative_capabilities<RosenbrockOf>();
     case MI355_OBJ_DIAG_QUADRATIC: return derivative_capabilities<DiagQuadraticOf>();
   }
-  if (objective >= MI355_OBJ_USER_FIRST && user_derivatives(objective) != nullptr)
-    return user_derivatives_capabilities(objective);
-  return -1;
+  int capabilities = 0;
+  return user_solver(objective, kUserDerivatives, &capabilities) != nullptr ? capabilities : -1;
 }
 
 int dispatch_derivatives(mi355_lbfgs_ctx* ctx, int phase, int W, int E, int objective, const DerivativeArgs& args,
@@ -46,10 +45,7 @@ int dispatch_derivatives(mi355_lbfgs_ctx* ctx, int phase, int W, int E, int obje
     case MI355_OBJ_ROSENBROCK: return launch_derivatives<RosenbrockOf>(ctx, phase, W, E, args, stream);
     case MI355_OBJ_DIAG_QUADRATIC: return launch_derivatives<DiagQuadraticOf>(ctx, phase, W, E, args, stream);
   }
-  if (objective >= MI355_OBJ_USER_FIRST) {
-    const UserDerivativesFn fn = user_derivatives(objective);
-    if (fn != nullptr) return fn(ctx, phase, W, E, args, stream);
-  }
+  if (const auto fn = user_solver_fn<kUserDerivatives>(objective)) return fn(ctx, phase, W, E, args, stream);
   return fail(MI355_ERR_UNSUPPORTED, derivative_unsupported_message(objective));
 }
 

@@ -19,18 +19,8 @@ struct DiagQuadraticOf {
 
 int dispatch_nelder_mead(mi355_lbfgs_ctx* ctx, int W, int objective, const SolveArgs& args,
                          const NelderMeadDeviceConfig& cfg, hipStream_t stream) {
-  switch (objective) {
-    case MI355_OBJ_ROSENBROCK:
-      return launch_nelder_mead_w<RosenbrockOf>(ctx, W, args, cfg, stream);
-    case MI355_OBJ_DIAG_QUADRATIC:
-      return launch_nelder_mead_w<DiagQuadraticOf>(ctx, W, args, cfg, stream);
-  }
-  if (objective >= MI355_OBJ_USER_FIRST) {
-    const UserNelderMeadFn fn = user_nelder_mead(objective);
-    if (fn != nullptr) return fn(ctx, W, args, cfg, stream);
-  }
-  return fail(MI355_ERR_INVALID_ARGUMENT,
-              "NelderMead is built for Rosenbrock, DiagQuadratic and user functors built with nelder_mead=True");
+  return dispatch_builtin_or_user<kUserNelderMead>(objective, &launch_nelder_mead_w<RosenbrockOf>, &launch_nelder_mead_w<DiagQuadraticOf>,
+                                                   ctx, W, args, cfg, stream);
 }
 
 }  // namespace mi355

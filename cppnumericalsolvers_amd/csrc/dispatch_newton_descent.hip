@@ -19,22 +19,8 @@ struct DiagQuadraticOf {
 
 int dispatch_newton_descent(mi355_lbfgs_ctx* ctx, int W, int objective, const SolveArgs& args,
                             const NewtonDescentDeviceConfig& cfg, hipStream_t stream) {
-  switch (objective) {
-    case MI355_OBJ_ROSENBROCK:
-      return launch_newton_descent_w<RosenbrockOf>(ctx, W, args, cfg, stream);
-    case MI355_OBJ_DIAG_QUADRATIC:
-      return launch_newton_descent_w<DiagQuadraticOf>(ctx, W, args, cfg, stream);
-  }
-  if (objective >= MI355_OBJ_USER_FIRST) {
-    const UserNewtonDescentFn fn = user_newton_descent(objective);
-    if (fn != nullptr) return fn(ctx, W, args, cfg, stream);
-    return fail(MI355_ERR_UNSUPPORTED,
-                "NewtonDescent: this library holds no Newton-descent kernel for this user objective (build it with "
-                "newton_descent=True and a functor that defines hess_full)");
-  }
-  return fail(MI355_ERR_UNSUPPORTED,
-              "NewtonDescent is built for objectives with a device Hessian (hess_full): Rosenbrock, DiagQuadratic and "
-              "user functors built with newton_descent=True; the ridge forms and the augmented-Lagrangian composite have none");
+  return dispatch_builtin_or_user<kUserNewtonDescent>(objective, &launch_newton_descent_w<RosenbrockOf>, &launch_newton_descent_w<DiagQuadraticOf>,
+                                                      ctx, W, args, cfg, stream);
 }
 
 }  // namespace mi355

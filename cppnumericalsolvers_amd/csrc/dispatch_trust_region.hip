@@ -19,22 +19,8 @@ struct DiagQuadraticOf {
 
 int dispatch_trust_region(mi355_lbfgs_ctx* ctx, int W, int objective, const SolveArgs& args,
                           const TrustRegionDeviceConfig& cfg, hipStream_t stream) {
-  switch (objective) {
-    case MI355_OBJ_ROSENBROCK:
-      return launch_trust_region_w<RosenbrockOf>(ctx, W, args, cfg, stream);
-    case MI355_OBJ_DIAG_QUADRATIC:
-      return launch_trust_region_w<DiagQuadraticOf>(ctx, W, args, cfg, stream);
-  }
-  if (objective >= MI355_OBJ_USER_FIRST) {
-    const UserTrustRegionFn fn = user_trust_region(objective);
-    if (fn != nullptr) return fn(ctx, W, args, cfg, stream);
-    return fail(MI355_ERR_UNSUPPORTED,
-                "TrustRegionNewton: this library holds no trust-region kernel for this user objective (build it with "
-                "trust_region=True and a functor that defines hess_full)");
-  }
-  return fail(MI355_ERR_UNSUPPORTED,
-              "TrustRegionNewton is built for objectives with a device Hessian (hess_full): Rosenbrock, DiagQuadratic and "
-              "user functors built with trust_region=True; the ridge forms and the augmented-Lagrangian composite have none");
+  return dispatch_builtin_or_user<kUserTrustRegion>(objective, &launch_trust_region_w<RosenbrockOf>, &launch_trust_region_w<DiagQuadraticOf>,
+                                                    ctx, W, args, cfg, stream);
 }
 
 }  // namespace mi355

@@ -1,7 +1,8 @@
 // engine_internal.hpp — shared by the translation units of libmi355_lbfgs.so.
 //
 // The library is built from several .hip files compiled in parallel (cppnumericalsolvers_amd/_build.py):
-// mi355_lbfgs.hip holds the C-ABI (validation, mapping choice, scratch), dispatch_w{8,16,32,64}.hip hold
+// mi355_lbfgs.hip holds the C-ABI (validation, mapping choice, scratch, the registry of user objectives),
+// solver_entry.hip the entry points of the five solvers that share solver_driver.hpp, dispatch_w{8,16,32,64}.hip hold
 // the solve / evaluation / line-search kernels of one lanes-per-problem value each, dispatch_lbfgsb.hip
 // the L-BFGS-B kernels.  Kernels are instantiated implicitly by the launch templates below, inside the
 // translation unit that calls dispatch_e<W> / dispatch_lbfgsb<E>.
@@ -200,65 +201,54 @@ struct UserObjectiveRegistration {
   }
 };
 
-// ... and the box-constrained solver on a user objective (registered by the 16-lane unit of the objective)
-// (W: lanes per problem, 16 or 32; E: coordinates per lane; args.relaxed selects the relaxed-algebra kernel.  The
-// generated unit holds the kernels of the shapes its `lbfgsb` key asked for and refuses the others.)
-using UserLbfgsbFn = int (*)(mi355_lbfgs_ctx* ctx, int W, int E, int linesearch, const LbfgsbArgs& args, hipStream_t stream);
-void register_user_lbfgsb(int objective_id, UserLbfgsbFn fn);
-struct UserLbfgsbRegistration {
-  UserLbfgsbRegistration(int objective_id, UserLbfgsbFn fn) { register_user_lbfgsb(objective_id, fn); }
-};
-
-// TrustRegionNewton (dispatch_trust_region.hip, trust_region_kernel.hpp): W lanes per problem, one coordinate per lane
-int dispatch_trust_region(mi355_lbfgs_ctx* ctx, int W, int objective, const SolveArgs& args,
-                          const TrustRegionDeviceConfig& cfg, hipStream_t stream);
-// ... on a user functor with a hess_full: registered by the unit _build.py generates for trust_region=True
-using UserTrustRegionFn = int (*)(mi355_lbfgs_ctx* ctx, int W, const SolveArgs& args, const TrustRegionDeviceConfig& cfg,
-                                  hipStream_t stream);
-void register_user_trust_region(int objective_id, UserTrustRegionFn fn);
-UserTrustRegionFn user_trust_region(int objective_id);
-struct UserTrustRegionRegistration {
-  UserTrustRegionRegistration(int objective_id, UserTrustRegionFn fn) { register_user_trust_region(objective_id, fn); }
-};
-
-// NelderMead (dispatch_nelder_mead.hip, nelder_mead_kernel.hpp): W lanes per problem, one coordinate per lane
-int dispatch_nelder_mead(mi355_lbfgs_ctx* ctx, int W, int objective, const SolveArgs& args,
-                         const NelderMeadDeviceConfig& cfg, hipStream_t stream);
-// ... on a user functor with a value entry: registered by the unit _build.py generates for nelder_mead=True
-using UserNelderMeadFn = int (*)(mi355_lbfgs_ctx* ctx, int W, const SolveArgs& args, const NelderMeadDeviceConfig& cfg,
-                                 hipStream_t stream);
-void register_user_nelder_mead(int objective_id, UserNelderMeadFn fn);
-UserNelderMeadFn user_nelder_mead(int objective_id);
-struct UserNelderMeadRegistration {
-  UserNelderMeadRegistration(int objective_id, UserNelderMeadFn fn) { register_user_nelder_mead(objective_id, fn); }
-};
-
-// NewtonDescent (dispatch_newton_descent.hip, newton_descent_kernel.hpp): W lanes per problem, one coordinate per lane
-int dispatch_newton_descent(mi355_lbfgs_ctx* ctx, int W, int objective, const SolveArgs& args,
-                            const NewtonDescentDeviceConfig& cfg, hipStream_t stream);
-// ... on a user functor with a hess_full: registered by the unit _build.py generates for newton_descent=True
-using UserNewtonDescentFn = int (*)(mi355_lbfgs_ctx* ctx, int W, const SolveArgs& args,
-                                    const NewtonDescentDeviceConfig& cfg, hipStream_t stream);
-void register_user_newton_descent(int objective_id, UserNewtonDescentFn fn);
-UserNewtonDescentFn user_newton_descent(int objective_id);
-struct UserNewtonDescentRegistration {
-  UserNewtonDescentRegistration(int objective_id, UserNewtonDescentFn fn) {
-    register_user_newton_descent(objective_id, fn);
+// Every other solver on a user objective: one slot per solver in the objective's registry entry, filled from a static
+// initialiser (a UserSolverRegistration) of the unit _build.py generates for that solver's key (lbfgsb=..., trust_region=True,
+// nelder_mead=True, newton_descent=True, first_order=True, derivatives=True).  UserSolverSignature<S>::Fn is the slot's
+// dispatch function: the solver's dispatch_* below without the objective id.
+//
+// The slots' arguments between ctx and stream — Lbfgsb: W (16 or 32), E, linesearch, args (args.relaxed selects the
+// relaxed-algebra kernel; the unit holds the kernels of the shapes its key asked for and refuses the others); the three
+// one-coordinate solvers: W, args, cfg; first order: method, W, E, args, cfg; derivatives: phase, W, E, args (and the unit
+// registers its capabilities: kDerivativeHasEval | kDerivativeHasHessFull of the functor).
+enum UserSolver { kUserLbfgsb, kUserTrustRegion, kUserNelderMead, kUserNewtonDescent, kUserFirstOrder, kUserDerivatives, kUserSolvers };
+template <class... A>
+using UserFn = int (*)(mi355_lbfgs_ctx* ctx, A..., hipStream_t stream);
+template <UserSolver S>
+struct UserSolverSignature;
+template <> struct UserSolverSignature<kUserLbfgsb> { using Fn = UserFn<int, int, int, const LbfgsbArgs&>; };
+template <> struct UserSolverSignature<kUserTrustRegion> { using Fn = UserFn<int, const SolveArgs&, const TrustRegionDeviceConfig&>; };
+template <> struct UserSolverSignature<kUserNelderMead> { using Fn = UserFn<int, const SolveArgs&, const NelderMeadDeviceConfig&>; };
+template <> struct UserSolverSignature<kUserNewtonDescent> { using Fn = UserFn<int, const SolveArgs&, const NewtonDescentDeviceConfig&>; };
+template <> struct UserSolverSignature<kUserFirstOrder> { using Fn = UserFn<int, int, int, const SolveArgs&, const FirstOrderDeviceConfig&>; };
+template <> struct UserSolverSignature<kUserDerivatives> { using Fn = UserFn<int, int, int, const DerivativeArgs&>; };
+using UserSolverFn = void (*)();   // what a slot stores: its Fn, cast back by user_solver_fn<S>
+void register_user_solver(int objective_id, UserSolver solver, UserSolverFn fn, int capabilities);
+// null: this library holds no kernel of `solver` for this objective; *capabilities: what the unit registered
+UserSolverFn user_solver(int objective_id, UserSolver solver, int* capabilities = nullptr);
+template <UserSolver S>
+struct UserSolverRegistration {
+  UserSolverRegistration(int objective_id, typename UserSolverSignature<S>::Fn fn, int capabilities = 0) {
+    register_user_solver(objective_id, S, reinterpret_cast<UserSolverFn>(fn), capabilities);
   }
 };
+using UserLbfgsbRegistration = UserSolverRegistration<kUserLbfgsb>;   // (the names the generated units of these two use)
+using UserDerivativesRegistration = UserSolverRegistration<kUserDerivatives>;
+template <UserSolver S>
+typename UserSolverSignature<S>::Fn user_solver_fn(int objective_id) {
+  return reinterpret_cast<typename UserSolverSignature<S>::Fn>(user_solver(objective_id, S));
+}
 
-// GradientDescent / ConjugatedGradientDescent (dispatch_first_order.hip, first_order_kernel.hpp): method = a
-// FirstOrderMethod, W lanes per problem, E coordinates per lane
+// The dispatch units of the five solvers that share csrc/solver_entry.hip (which has refused every objective but
+// Rosenbrock, DiagQuadratic and a user functor with a registered slot).  W lanes per problem, E coordinates per lane (one
+// where there is no E); method = a FirstOrderMethod.
+int dispatch_trust_region(mi355_lbfgs_ctx* ctx, int W, int objective, const SolveArgs& args,
+                          const TrustRegionDeviceConfig& cfg, hipStream_t stream);
+int dispatch_nelder_mead(mi355_lbfgs_ctx* ctx, int W, int objective, const SolveArgs& args,
+                         const NelderMeadDeviceConfig& cfg, hipStream_t stream);
+int dispatch_newton_descent(mi355_lbfgs_ctx* ctx, int W, int objective, const SolveArgs& args,
+                            const NewtonDescentDeviceConfig& cfg, hipStream_t stream);
 int dispatch_first_order(mi355_lbfgs_ctx* ctx, int method, int W, int E, int objective, const SolveArgs& args,
                          const FirstOrderDeviceConfig& cfg, hipStream_t stream);
-// ... on a user functor: registered by the unit _build.py generates for first_order=True
-using UserFirstOrderFn = int (*)(mi355_lbfgs_ctx* ctx, int method, int W, int E, const SolveArgs& args,
-                                 const FirstOrderDeviceConfig& cfg, hipStream_t stream);
-void register_user_first_order(int objective_id, UserFirstOrderFn fn);
-UserFirstOrderFn user_first_order(int objective_id);
-struct UserFirstOrderRegistration {
-  UserFirstOrderRegistration(int objective_id, UserFirstOrderFn fn) { register_user_first_order(objective_id, fn); }
-};
 
 // The derivative checker (dispatch_derivatives.hip, derivative_check_kernel.hpp): phase = a DerivativePhase, W lanes per
 // point, E coordinates per lane (1 for the Hessian phases)
@@ -269,18 +259,12 @@ int derivative_capabilities_of(int objective);
 const char* derivative_unsupported_message(int objective);
 int derivative_report_init(mi355_derivative_report* report, long long B, hipStream_t stream);
 int derivative_compare(const DerivativeCompareArgs& args, bool hessian, hipStream_t stream);
-// ... on a user functor: registered by the unit _build.py generates for derivatives=True
-using UserDerivativesFn = int (*)(mi355_lbfgs_ctx* ctx, int phase, int W, int E, const DerivativeArgs& args,
-                                  hipStream_t stream);
-void register_user_derivatives(int objective_id, UserDerivativesFn fn, int capabilities);
-UserDerivativesFn user_derivatives(int objective_id);
-int user_derivatives_capabilities(int objective_id);
-struct UserDerivativesRegistration {
-  UserDerivativesRegistration(int objective_id, UserDerivativesFn fn, int capabilities) {
-    register_user_derivatives(objective_id, fn, capabilities);
-  }
-};
 
+// Shared by the entry points of mi355_lbfgs.hip and solver_entry.hip.  validate: the desc checks every solve entry point
+// runs (dimensions above MI355_LBFGS_MAX_N exist for the Lbfgs entry points only: allow_wide).  upload_params: the
+// objective's parameter blob, re-laid out for the (W, E) mapping where the objective asks for it, into ctx->params_dev.
+int validate(const mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, long long B, bool allow_wide = false);
+int upload_params(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int W, int E, hipStream_t stream);
 // desc->trace (device array pointers) -> the trace fields of SolveArgs; uploads the problem list, zeroes `written`
 int setup_trace(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, hipStream_t stream, SolveArgs& args);
 // frees what host_pipeline.hip hangs on a context

@@ -1,5 +1,7 @@
 // mi355_lbfgs.hip — implementation of the C-ABI in include/mi355_lbfgs.h:
-// argument validation, (W, E) mapping choice, kernel dispatch, device scratch.
+// argument validation, (W, E) mapping choice, kernel dispatch, device scratch, the registry of user objectives.
+// The entry points of TrustRegionNewton, NewtonDescent, NelderMead and the first-order solvers are solver_entry.hip;
+// validate() and upload_params() serve both files.
 // gfx950 only; no CPU fallback anywhere in this file.
 #include <cmath>
 #include <cstdio>
@@ -27,13 +29,8 @@ int fail(int code, const std::string& msg) {
 namespace {
 struct UserEntry {
   UserDispatchFn fn[4] = {nullptr, nullptr, nullptr, nullptr};  // lanes per problem 8, 16, 32, 64
-  UserLbfgsbFn lbfgsb = nullptr;
-  UserTrustRegionFn trust_region = nullptr;
-  UserNelderMeadFn nelder_mead = nullptr;
-  UserNewtonDescentFn newton_descent = nullptr;
-  UserFirstOrderFn first_order = nullptr;
-  UserDerivativesFn derivatives = nullptr;
-  int derivatives_capabilities = 0;
+  UserSolverFn solver[kUserSolvers] = {};  // the other solvers' slots (engine_internal.hpp, UserSolver)
+  int capabilities[kUserSolvers] = {};
   std::string name;
 };
 std::vector<std::pair<int, UserEntry>>& user_table() {
@@ -68,40 +65,18 @@ UserEntry* user_entry(int objective_id) {
   user_table().emplace_back(objective_id, UserEntry());
   return &user_table().back().second;
 }
-// what a registered entry holds in `member`, or `none`
-template <class T>
-T user_lookup(int objective_id, T UserEntry::*member, T none) {
-  const UserEntry* u = find_user_objective(objective_id);
-  return u ? u->*member : none;
-}
 }  // namespace
-void register_user_lbfgsb(int objective_id, UserLbfgsbFn fn) {
-  if (UserEntry* u = user_entry(objective_id)) u->lbfgsb = fn;
-}
-void register_user_trust_region(int objective_id, UserTrustRegionFn fn) {
-  if (UserEntry* u = user_entry(objective_id)) u->trust_region = fn;
-}
-UserTrustRegionFn user_trust_region(int id) { return user_lookup<UserTrustRegionFn>(id, &UserEntry::trust_region, nullptr); }
-void register_user_nelder_mead(int objective_id, UserNelderMeadFn fn) {
-  if (UserEntry* u = user_entry(objective_id)) u->nelder_mead = fn;
-}
-UserNelderMeadFn user_nelder_mead(int id) { return user_lookup<UserNelderMeadFn>(id, &UserEntry::nelder_mead, nullptr); }
-void register_user_newton_descent(int objective_id, UserNewtonDescentFn fn) {
-  if (UserEntry* u = user_entry(objective_id)) u->newton_descent = fn;
-}
-UserNewtonDescentFn user_newton_descent(int id) { return user_lookup<UserNewtonDescentFn>(id, &UserEntry::newton_descent, nullptr); }
-void register_user_first_order(int objective_id, UserFirstOrderFn fn) {
-  if (UserEntry* u = user_entry(objective_id)) u->first_order = fn;
-}
-UserFirstOrderFn user_first_order(int id) { return user_lookup<UserFirstOrderFn>(id, &UserEntry::first_order, nullptr); }
-void register_user_derivatives(int objective_id, UserDerivativesFn fn, int capabilities) {
+void register_user_solver(int objective_id, UserSolver solver, UserSolverFn fn, int capabilities) {
   if (UserEntry* u = user_entry(objective_id)) {
-    u->derivatives = fn;
-    u->derivatives_capabilities = capabilities;
+    u->solver[solver] = fn;
+    u->capabilities[solver] = capabilities;
   }
 }
-UserDerivativesFn user_derivatives(int id) { return user_lookup<UserDerivativesFn>(id, &UserEntry::derivatives, nullptr); }
-int user_derivatives_capabilities(int id) { return user_lookup<int>(id, &UserEntry::derivatives_capabilities, 0); }
+UserSolverFn user_solver(int objective_id, UserSolver solver, int* capabilities) {
+  const UserEntry* u = find_user_objective(objective_id);
+  if (u && capabilities) *capabilities = u->capabilities[solver];
+  return u ? u->solver[solver] : nullptr;
+}
 }  // namespace mi355
 
 namespace {
@@ -228,7 +203,10 @@ int n_params_expected(const mi355_lbfgs_desc* desc) {
   return -1;
 }
 
-int validate(const mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, long long B, bool allow_wide = false) {
+}  // namespace
+
+namespace mi355 {   // (declared in engine_internal.hpp: solver_entry.hip runs them too)
+int validate(const mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, long long B, bool allow_wide) {
   if (!ctx) return fail(MI355_ERR_INVALID_ARGUMENT, "null context");
   if (!desc) return fail(MI355_ERR_INVALID_ARGUMENT, "null desc");
   if (B < 0) return fail(MI355_ERR_INVALID_ARGUMENT, "negative batch size");
@@ -343,6 +321,9 @@ int upload_params(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int W, int
   ctx->params_stream = stream;
   return MI355_OK;
 }
+}  // namespace mi355
+
+namespace {
 
 // lbfgs.h:126-131: preconditioner_j = 1 / (|H_jj| + eps), IEEE division on the host; *out = null for First mode
 int upload_precond(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, hipStream_t stream, const double** out) {
@@ -907,10 +888,9 @@ extern "C" int mi355_lbfgsb_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbf
   args.upper = upper;
   args.relaxed = use_fast ? 1 : 0;
   if (desc->objective >= MI355_OBJ_USER_FIRST) {
-    const UserEntry* u = find_user_objective(desc->objective);
-    if (!u || !u->lbfgsb)
-      return fail(MI355_ERR_UNSUPPORTED, "no user objective with this id is compiled into this library for L-BFGS-B");
-    return u->lbfgsb(ctx, two_rows ? 32 : 16, E, desc->linesearch, args, stream);   // (refuses shapes it was not built for)
+    const auto fn = user_solver_fn<kUserLbfgsb>(desc->objective);
+    if (!fn) return fail(MI355_ERR_UNSUPPORTED, "no user objective with this id is compiled into this library for L-BFGS-B");
+    return fn(ctx, two_rows ? 32 : 16, E, desc->linesearch, args, stream);   // (refuses shapes it was not built for)
   }
   // the shapes added in round 3 (history sizes 6..10 above n = 64, under Hager-Zhang and on the ridge objective)
   const bool ridge = desc->objective == MI355_OBJ_SQUARED_ERROR_RIDGE;
@@ -1232,361 +1212,6 @@ int mi355_lbfgs_selftest(mi355_lbfgs_ctx* ctx, int32_t* lane_maps, const double*
 }
 
 }  // extern "C"
-
-// ---- shared by the entry points of TrustRegionNewton, NelderMead, NewtonDescent and the first-order solvers -----------
-namespace {
-// lanes per problem of a one-coordinate-per-lane solver (n <= 64): the padded width of n where the caller leaves it to the
-// library (0), else the caller's, which must be one of 8 / 16 / 32 / 64 and cover n; 0: it is not
-int lanes_covering(int requested, int n) {
-  if (requested == 0) {
-    int W = 8;
-    while (W < n) W <<= 1;
-    return W;
-  }
-  const bool built = requested == 8 || requested == 16 || requested == 32 || requested == 64;
-  return (built && requested >= n) ? requested : 0;
-}
-
-// the kernel arguments every one of these solvers fills the same way (m means nothing to them; the parameter blob is
-// the one upload_params left in the context)
-SolveArgs solver_args(const mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc& desc, int64_t B, const double* x0, double* x_out,
-                      double* f_out, double* g_out, mi355_lbfgs_progress* progress_out) {
-  SolveArgs args;
-  std::memset(&args, 0, sizeof(args));
-  args.x0 = x0;
-  args.x_out = x_out;
-  args.f_out = f_out;
-  args.g_out = g_out;
-  args.progress_out = progress_out;
-  args.obj_params = ctx->params_dev;
-  args.per_problem = desc.per_problem_data;
-  args.per_problem_stride = desc.per_problem_stride;
-  args.B = B;
-  args.n = desc.n;
-  args.m = 1;
-  args.stop = desc.stop;
-  return args;
-}
-}  // namespace
-
-// ---- TrustRegionNewton (trust_region_kernel.hpp) -------------------------------------------------------------------
-extern "C" int mi355_trust_region_default_config(mi355_trust_region_config* out) {
-  if (!out) return fail(MI355_ERR_INVALID_ARGUMENT, "null config");
-  out->initial_radius = 1.0;        // trust_region_newton.h TrustRegionNewtonConfig defaults
-  out->max_radius = 1e10;
-  out->acceptance_threshold = 0.15;
-  out->shrink_factor = 0.25;
-  out->expand_factor = 2.0;
-  out->rho_low = 0.25;
-  out->rho_high = 0.75;
-  out->cg_forcing_coefficient = 0.5;
-  out->cg_max_iterations_floor = 10;
-  out->min_radius = 1e-12;
-  out->rejection_retry_limit = 50;
-  return MI355_OK;
-}
-
-extern "C" int mi355_trust_region_newton_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc_in,
-                                                        const mi355_trust_region_config* config, int64_t B,
-                                                        const double* x0, double* x_out, double* f_out, double* g_out,
-                                                        mi355_lbfgs_progress* progress_out, void* stream_) {
-  if (!desc_in) return fail(MI355_ERR_INVALID_ARGUMENT, "null desc");
-  // m and the line search mean nothing to this solver; the Hessian always comes from the functor
-  mi355_lbfgs_desc desc = *desc_in;
-  desc.m = 1;
-  desc.linesearch = MI355_LS_MORE_THUENTE;
-  desc.history_placement = 0;
-  if (desc.hessian_diagonal != nullptr)
-    return fail(MI355_ERR_INVALID_ARGUMENT, "TrustRegionNewton: H(x) comes from the device functor (hessian_diagonal NULL)");
-  desc.hessian_from_functor = 1;
-  if (desc.n > kHessianConditionMaxN)
-    return fail(MI355_ERR_UNSUPPORTED, "TrustRegionNewton is built for n <= 64 (H is n x n in LDS per problem)");
-  int rc = validate(ctx, &desc, B);
-  if (rc != MI355_OK) return rc;
-  if (desc.arithmetic == MI355_ARITH_FMA)
-    return fail(MI355_ERR_UNSUPPORTED, "TrustRegionNewton is built for the exact arithmetic only (no MI355_ARITH_FMA)");
-  if (desc.objective != MI355_OBJ_ROSENBROCK && desc.objective != MI355_OBJ_DIAG_QUADRATIC &&
-      !(desc.objective >= MI355_OBJ_USER_FIRST && user_trust_region(desc.objective) != nullptr))
-    return fail(MI355_ERR_UNSUPPORTED,
-                desc.objective >= MI355_OBJ_USER_FIRST
-                    ? "TrustRegionNewton: this library holds no trust-region kernel for this user objective (build it with "
-                      "trust_region=True and a functor that defines hess_full)"
-                    : "TrustRegionNewton is built for objectives with a device Hessian (hess_full): Rosenbrock, "
-                      "DiagQuadratic and user functors; the ridge forms, the augmented-Lagrangian composite and sum / "
-                      "product records have none");
-  if (desc.elems_per_lane != 0 && desc.elems_per_lane != 1)
-    return fail(MI355_ERR_INVALID_ARGUMENT, "TrustRegionNewton: one coordinate per lane (elems_per_lane 0 or 1)");
-  const int W = lanes_covering(desc.lanes_per_problem, desc.n);
-  if (W == 0)
-    return fail(MI355_ERR_INVALID_ARGUMENT, "TrustRegionNewton: lanes_per_problem must be 8, 16, 32 or 64 and cover n");
-  mi355_trust_region_config c;
-  mi355_trust_region_default_config(&c);
-  if (config) c = *config;
-  TrustRegionDeviceConfig dc;
-  dc.initial_radius = c.initial_radius;
-  dc.max_radius = c.max_radius;
-  dc.acceptance_threshold = c.acceptance_threshold;
-  dc.shrink_factor = c.shrink_factor;
-  dc.expand_factor = c.expand_factor;
-  dc.rho_low = c.rho_low;
-  dc.rho_high = c.rho_high;
-  dc.cg_forcing_coefficient = c.cg_forcing_coefficient;
-  dc.min_radius = c.min_radius;
-  dc.cg_extra_iterations = c.cg_max_iterations_floor > 0 ? c.cg_max_iterations_floor : 0;
-  dc.rejection_retry_limit = c.rejection_retry_limit < 0 ? 0 : (c.rejection_retry_limit > 1000 ? 1000 : c.rejection_retry_limit);
-  if (B == 0) return MI355_OK;
-  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  MI355_ENTER_DEVICE(ctx);
-  rc = upload_params(ctx, &desc, W, 1, stream);
-  if (rc != MI355_OK) return rc;
-  SolveArgs args = solver_args(ctx, desc, B, x0, x_out, f_out, g_out, progress_out);
-  args.hess_from_functor = 1;
-  args.hessian_condition_stop = desc.hessian_condition_stop;
-  rc = setup_trace(ctx, &desc, B, stream, args);
-  if (rc != MI355_OK) return rc;
-  return dispatch_trust_region(ctx, W, desc.objective, args, dc, stream);
-}
-
-// ---- NelderMead (nelder_mead_kernel.hpp) ---------------------------------------------------------------------------
-extern "C" int mi355_nelder_mead_default_config(mi355_nelder_mead_config* out) {
-  if (!out) return fail(MI355_ERR_INVALID_ARGUMENT, "null config");
-  out->rho = 1.0;             // nelder_mead.h:58-64
-  out->xi = 20.0;
-  out->gamma = 0.1;
-  out->sigma = 0.5;
-  out->degenerate_tol = 1e-8;
-  out->mode = MI355_NM_MODE_VALUE;
-  return MI355_OK;
-}
-
-extern "C" int mi355_nelder_mead_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc_in,
-                                                const mi355_nelder_mead_config* config, int64_t B, const double* x0,
-                                                double* x_out, double* f_out, double* g_out,
-                                                mi355_lbfgs_progress* progress_out, void* stream_) {
-  if (!desc_in) return fail(MI355_ERR_INVALID_ARGUMENT, "null desc");
-  // m, the line search and every Hessian field mean nothing to a derivative-free solver
-  mi355_lbfgs_desc desc = *desc_in;
-  desc.m = 1;
-  desc.linesearch = MI355_LS_MORE_THUENTE;
-  desc.history_placement = 0;
-  desc.hessian_diagonal = nullptr;
-  desc.hessian_from_functor = 0;
-  desc.hessian_condition_stop = 0.0;
-  if (desc.n > 64)
-    return fail(MI355_ERR_INVALID_ARGUMENT, "NelderMead is built for n <= 64 (the simplex is n x (n + 1) in LDS per problem)");
-  if (desc.objective != MI355_OBJ_ROSENBROCK && desc.objective != MI355_OBJ_DIAG_QUADRATIC &&
-      !(desc.objective >= MI355_OBJ_USER_FIRST && user_nelder_mead(desc.objective) != nullptr))
-    return fail(MI355_ERR_INVALID_ARGUMENT,
-                desc.objective >= MI355_OBJ_USER_FIRST
-                    ? "NelderMead: this library holds no Nelder-Mead kernel for this user objective (build it with "
-                      "nelder_mead=True and a functor that defines value)"
-                    : "NelderMead is built for Rosenbrock, DiagQuadratic and user functors built with nelder_mead=True");
-  if (desc.arithmetic == MI355_ARITH_FMA)
-    return fail(MI355_ERR_INVALID_ARGUMENT, "NelderMead is built for the exact arithmetic only (no MI355_ARITH_FMA)");
-  int rc = validate(ctx, &desc, B);
-  if (rc != MI355_OK) return rc;
-  if (desc.elems_per_lane != 0 && desc.elems_per_lane != 1)
-    return fail(MI355_ERR_INVALID_ARGUMENT, "NelderMead: one coordinate per lane (elems_per_lane 0 or 1)");
-  const int W = lanes_covering(desc.lanes_per_problem, desc.n);
-  if (W == 0)
-    return fail(MI355_ERR_INVALID_ARGUMENT, "NelderMead: lanes_per_problem must be 8, 16, 32 or 64 and cover n");
-  mi355_nelder_mead_config c;
-  mi355_nelder_mead_default_config(&c);
-  if (config) c = *config;
-  if (c.mode != MI355_NM_MODE_VALUE && c.mode != MI355_NM_MODE_FIRST)
-    return fail(MI355_ERR_INVALID_ARGUMENT, "NelderMead: mode must be MI355_NM_MODE_VALUE or MI355_NM_MODE_FIRST");
-  NelderMeadDeviceConfig dc;
-  dc.rho = c.rho;
-  dc.xi = c.xi;
-  dc.gamma = c.gamma;
-  dc.sigma = c.sigma;
-  dc.degenerate_tol = c.degenerate_tol;
-  dc.first_mode = c.mode == MI355_NM_MODE_FIRST ? 1 : 0;
-  if (B == 0) return MI355_OK;
-  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  MI355_ENTER_DEVICE(ctx);
-  rc = upload_params(ctx, &desc, W, 1, stream);
-  if (rc != MI355_OK) return rc;
-  SolveArgs args = solver_args(ctx, desc, B, x0, x_out, f_out, g_out, progress_out);
-  rc = setup_trace(ctx, &desc, B, stream, args);
-  if (rc != MI355_OK) return rc;
-  return dispatch_nelder_mead(ctx, W, desc.objective, args, dc, stream);
-}
-
-// ---- NewtonDescent (newton_descent_kernel.hpp) ---------------------------------------------------------------------
-extern "C" int mi355_newton_descent_default_config(mi355_newton_descent_config* out) {
-  if (!out) return fail(MI355_ERR_INVALID_ARGUMENT, "null config");
-  out->safe_guard = 1e-5;   // newton_descent.h:69
-  out->armijo_c = 0.2;      // linesearch/armijo.h:85-86
-  out->armijo_rho = 0.9;
-  return MI355_OK;
-}
-
-extern "C" int mi355_newton_descent_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc_in,
-                                                   const mi355_newton_descent_config* config, int64_t B,
-                                                   const double* x0, double* x_out, double* f_out, double* g_out,
-                                                   mi355_lbfgs_progress* progress_out, void* stream_) {
-  if (!desc_in) return fail(MI355_ERR_INVALID_ARGUMENT, "null desc");
-  // m and the line search field mean nothing to this solver; the Hessian always comes from the functor
-  mi355_lbfgs_desc desc = *desc_in;
-  desc.m = 1;
-  desc.linesearch = MI355_LS_MORE_THUENTE;
-  desc.history_placement = 0;
-  if (desc.hessian_diagonal != nullptr)
-    return fail(MI355_ERR_INVALID_ARGUMENT, "NewtonDescent: H(x) comes from the device functor (hessian_diagonal NULL)");
-  desc.hessian_from_functor = 1;
-  if (desc.n > 64)
-    return fail(MI355_ERR_UNSUPPORTED, "NewtonDescent is built for n <= 64 (H and its LU are n x n in LDS per problem)");
-  int rc = validate(ctx, &desc, B);
-  if (rc != MI355_OK) return rc;
-  if (desc.arithmetic == MI355_ARITH_FMA)
-    return fail(MI355_ERR_UNSUPPORTED, "NewtonDescent is built for the exact arithmetic only (no MI355_ARITH_FMA)");
-  if (desc.objective != MI355_OBJ_ROSENBROCK && desc.objective != MI355_OBJ_DIAG_QUADRATIC &&
-      !(desc.objective >= MI355_OBJ_USER_FIRST && user_newton_descent(desc.objective) != nullptr))
-    return fail(MI355_ERR_UNSUPPORTED,
-                desc.objective >= MI355_OBJ_USER_FIRST
-                    ? "NewtonDescent: this library holds no Newton-descent kernel for this user objective (build it with "
-                      "newton_descent=True and a functor that defines hess_full)"
-                    : "NewtonDescent is built for objectives with a device Hessian (hess_full): Rosenbrock, "
-                      "DiagQuadratic and user functors; the ridge forms, the augmented-Lagrangian composite and sum / "
-                      "product records have none");
-  if (desc.elems_per_lane != 0 && desc.elems_per_lane != 1)
-    return fail(MI355_ERR_INVALID_ARGUMENT, "NewtonDescent: one coordinate per lane (elems_per_lane 0 or 1)");
-  int W = lanes_covering(desc.lanes_per_problem, desc.n);
-  if (W == 0)
-    return fail(MI355_ERR_INVALID_ARGUMENT, "NewtonDescent: lanes_per_problem must be 8, 16, 32 or 64 and cover n");
-  // the library's choice is the padded width, except 16 < n <= 32: 64 lanes measured faster there (one problem per
-  // wavefront halves the LDS per wavefront; profiles/newton_descent_bench.jsonl)
-  if (desc.lanes_per_problem == 0 && W == 32) W = 64;
-  mi355_newton_descent_config c;
-  mi355_newton_descent_default_config(&c);
-  if (config) c = *config;
-  NewtonDescentDeviceConfig dc;
-  dc.safe_guard = c.safe_guard;
-  dc.armijo_c = c.armijo_c;
-  dc.armijo_rho = c.armijo_rho;
-  if (B == 0) return MI355_OK;
-  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  MI355_ENTER_DEVICE(ctx);
-  rc = upload_params(ctx, &desc, W, 1, stream);
-  if (rc != MI355_OK) return rc;
-  SolveArgs args = solver_args(ctx, desc, B, x0, x_out, f_out, g_out, progress_out);
-  args.hess_from_functor = 1;
-  args.hessian_condition_stop = desc.hessian_condition_stop;
-  rc = setup_trace(ctx, &desc, B, stream, args);
-  if (rc != MI355_OK) return rc;
-  return dispatch_newton_descent(ctx, W, desc.objective, args, dc, stream);
-}
-
-// ---- GradientDescent / ConjugatedGradientDescent (first_order_kernel.hpp) -------------------------------------------
-extern "C" int mi355_armijo_default_config(mi355_armijo_config* out) {
-  if (!out) return fail(MI355_ERR_INVALID_ARGUMENT, "null config");
-  out->c = 0.2;            // linesearch/armijo.h:49-50
-  out->rho = 0.9;
-  out->alpha_min = 1e-8;   // :56
-  return MI355_OK;
-}
-
-namespace {
-int first_order_minimize_batch(const char* solver, int method, mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc_in,
-                               const mi355_armijo_config* config, int64_t B, const double* x0, double* x_out,
-                               double* f_out, double* g_out, mi355_lbfgs_progress* progress_out, void* stream_) {
-  if (!desc_in) return fail(MI355_ERR_INVALID_ARGUMENT, "null desc");
-  // m, the line search field and the Hessian fields mean nothing to these solvers
-  mi355_lbfgs_desc desc = *desc_in;
-  desc.m = 1;
-  desc.linesearch = MI355_LS_MORE_THUENTE;
-  desc.history_placement = 0;
-  desc.hessian_from_functor = 0;
-  desc.hessian_diagonal = nullptr;
-  static thread_local std::string msg;
-  if (desc.hessian_condition_stop != 0.0) {
-    msg = std::string(solver) + ": the condition_hessian test is not evaluated (hessian_condition_stop must be 0)";
-    return fail(MI355_ERR_INVALID_ARGUMENT, msg.c_str());
-  }
-  if (desc.n > MI355_LBFGS_MAX_N) {
-    msg = std::string(solver) + " is built for n <= 256 (x, g and d in registers, up to four coordinates per lane)";
-    return fail(MI355_ERR_UNSUPPORTED, msg.c_str());
-  }
-  int rc = validate(ctx, &desc, B);
-  if (rc != MI355_OK) return rc;
-  if (desc.arithmetic == MI355_ARITH_FMA) {
-    msg = std::string(solver) + " is built for the exact arithmetic only (no MI355_ARITH_FMA)";
-    return fail(MI355_ERR_UNSUPPORTED, msg.c_str());
-  }
-  if (desc.objective != MI355_OBJ_ROSENBROCK && desc.objective != MI355_OBJ_DIAG_QUADRATIC &&
-      !(desc.objective >= MI355_OBJ_USER_FIRST && user_first_order(desc.objective) != nullptr)) {
-    msg = std::string(solver) +
-          (desc.objective >= MI355_OBJ_USER_FIRST
-               ? ": this library holds no first-order kernel for this user objective (build it with first_order=True)"
-               : " is built for objectives without LDS data: Rosenbrock, DiagQuadratic and user functors built with "
-                 "first_order=True; not the ridge forms or the augmented-Lagrangian composite");
-    return fail(MI355_ERR_UNSUPPORTED, msg.c_str());
-  }
-  // the mapping: the padded width at one coordinate per lane up to 64, then 64 lanes at two and four
-  int W = desc.lanes_per_problem, E = desc.elems_per_lane;
-  if (W == 0) {
-    if (E != 0) {
-      msg = std::string(solver) + ": elems_per_lane needs an explicit lanes_per_problem";
-      return fail(MI355_ERR_INVALID_ARGUMENT, msg.c_str());
-    }
-    W = 8;
-    while (W < desc.n && W < 64) W <<= 1;
-  } else if (!(W == 8 || W == 16 || W == 32 || W == 64)) {
-    msg = std::string(solver) + ": lanes_per_problem must be 0, 8, 16, 32 or 64";
-    return fail(MI355_ERR_INVALID_ARGUMENT, msg.c_str());
-  }
-  if (E == 0) E = (desc.n <= W) ? 1 : ((desc.n <= 2 * W) ? 2 : 4);
-  if (!(E == 1 || ((E == 2 || E == 4) && W == 64)) || W * E < desc.n) {
-    msg = std::string(solver) +
-          ": the mapping must cover n with 8, 16, 32 or 64 lanes at one coordinate per lane, or 64 lanes at two or four";
-    return fail(MI355_ERR_INVALID_ARGUMENT, msg.c_str());
-  }
-  mi355_armijo_config c;
-  mi355_armijo_default_config(&c);
-  if (config) c = *config;
-  // (the search must end: alpha shrinks towards alpha_min)
-  if (!(c.rho > 0.0 && c.rho < 1.0) || !(c.alpha_min > 0.0)) {
-    msg = std::string(solver) + ": the Armijo config needs 0 < rho < 1 and alpha_min > 0";
-    return fail(MI355_ERR_INVALID_ARGUMENT, msg.c_str());
-  }
-  FirstOrderDeviceConfig dc;
-  dc.armijo_c = c.c;
-  dc.armijo_rho = c.rho;
-  dc.armijo_alpha_min = c.alpha_min;
-  // measurement switch (scripts/first_order_bench.py): 1 = the Armijo trials run eval instead of value()
-  dc.eval_trials = ctx->debug_cg_eval_trials ? 1 : 0;
-  if (B == 0) return MI355_OK;
-  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  MI355_ENTER_DEVICE(ctx);
-  rc = upload_params(ctx, &desc, W, E, stream);
-  if (rc != MI355_OK) return rc;
-  SolveArgs args = solver_args(ctx, desc, B, x0, x_out, f_out, g_out, progress_out);
-  rc = setup_trace(ctx, &desc, B, stream, args);
-  if (rc != MI355_OK) return rc;
-  return dispatch_first_order(ctx, method, W, E, desc.objective, args, dc, stream);
-}
-}  // namespace
-
-extern "C" int mi355_gradient_descent_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B,
-                                                     const double* x0, double* x_out, double* f_out, double* g_out,
-                                                     mi355_lbfgs_progress* progress_out, void* stream) {
-  return first_order_minimize_batch("GradientDescent", kGradientDescent, ctx, desc, nullptr, B, x0, x_out, f_out, g_out,
-                                    progress_out, stream);
-}
-
-extern "C" int mi355_conjugated_gradient_descent_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc,
-                                                                const mi355_armijo_config* config, int64_t B,
-                                                                const double* x0, double* x_out, double* f_out,
-                                                                double* g_out, mi355_lbfgs_progress* progress_out,
-                                                                void* stream) {
-  return first_order_minimize_batch("ConjugatedGradientDescent", kConjugatedGradientDescent, ctx, desc, config, B, x0,
-                                    x_out, f_out, g_out, progress_out, stream);
-}
 
 // ---- derivative check of a device functor (derivative_check_kernel.hpp) ----------------------------------------------
 extern "C" int mi355_derivative_default_config(mi355_derivative_config* out) {

@@ -1,6 +1,6 @@
 // nelder_mead_launch.hpp — launch of the Nelder-Mead kernel (nelder_mead_kernel.hpp) for one functor type, shared by
-// dispatch_nelder_mead.hip (built-in objectives) and the units _build.py generates for user functors: the pre-checks, the
-// mode and the LDS size here, the persistent-grid launch in solver_launch.hpp.
+// dispatch_nelder_mead.hip (built-in objectives) and the units _build.py generates for user functors: the mode, the
+// LDS size and its limit here, the persistent-grid launch in solver_launch.hpp.
 #pragma once
 #include "nelder_mead_kernel.hpp"
 #include "solver_launch.hpp"
@@ -11,7 +11,6 @@ template <int W, class Obj, bool FIRST>
 int launch_nelder_mead_mode(mi355_lbfgs_ctx* ctx, const SolveArgs& args, const NelderMeadDeviceConfig& cfg,
                             hipStream_t stream) {
   constexpr int kLdsLimit = 160 * 1024;
-  if (args.n > W) return fail(MI355_ERR_INVALID_ARGUMENT, "NelderMead: lanes_per_problem must cover n");
   const int lds = (kWave / W) * nelder_mead_lds_doubles(args.n, W) * static_cast<int>(sizeof(double));
   if (lds > kLdsLimit) return fail(MI355_ERR_INVALID_ARGUMENT, "NelderMead: the simplices do not fit LDS");
   return launch_persistent_solver<W, 1>(ctx, nelder_mead_kernel<W, Obj, FIRST>, lds, args, cfg, stream);
@@ -32,13 +31,9 @@ int launch_nelder_mead(mi355_lbfgs_ctx* ctx, const SolveArgs& args, const Nelder
 template <template <int, int> class ObjOf>
 int launch_nelder_mead_w(mi355_lbfgs_ctx* ctx, int W, const SolveArgs& args, const NelderMeadDeviceConfig& cfg,
                          hipStream_t stream) {
-  switch (W) {
-    case 8: return launch_nelder_mead<8, typename ObjOf<8, 1>::type>(ctx, args, cfg, stream);
-    case 16: return launch_nelder_mead<16, typename ObjOf<16, 1>::type>(ctx, args, cfg, stream);
-    case 32: return launch_nelder_mead<32, typename ObjOf<32, 1>::type>(ctx, args, cfg, stream);
-    case 64: return launch_nelder_mead<64, typename ObjOf<64, 1>::type>(ctx, args, cfg, stream);
-  }
-  return fail(MI355_ERR_INVALID_ARGUMENT, "NelderMead: lanes_per_problem must be 8, 16, 32 or 64");
+  return launch_for_lanes(W, [&](auto w) {
+    return launch_nelder_mead<decltype(w)::value, typename ObjOf<decltype(w)::value, 1>::type>(ctx, args, cfg, stream);
+  });
 }
 
 }  // namespace mi355
