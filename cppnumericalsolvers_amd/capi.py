@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "mi355_lbfgs_abi_version", "mi355_auglag_family_capacity", "mi355_lbfgs_create", "mi355_lbfgs_destroy", "mi355_lbfgs_last_error",
     "mi355_lbfgs_default_stop", "mi355_lbfgs_minimize_batch", "mi355_lbfgs_minimize_batch_host",
     "mi355_lbfgsb_minimize_batch", "mi355_lbfgsb_minimize_batch_host",
+    "mi355_lbfgsb_minimize_batch_boxes", "mi355_lbfgsb_minimize_batch_boxes_host",
     "mi355_bfgs_minimize_batch", "mi355_bfgs_minimize_batch_host",
     "mi355_lbfgs_last_kernel_ms", "mi355_lbfgs_last_launch", "mi355_lbfgs_last_arithmetic", "mi355_lbfgs_last_kernel_variant",
     "mi355_lbfgs_hessian_condition",
@@ -299,6 +300,8 @@ def _bind(L):
                                                      C.c_int64] + [vp] * 7
     L.mi355_lbfgsb_minimize_batch.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mi355_lbfgsb_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, vp, vp, vp, vp, vp]
+    L.mi355_lbfgsb_minimize_batch_boxes.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.mi355_lbfgsb_minimize_batch_boxes_host.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp]
     L.mi355_lbfgs_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.mi355_lbfgs_last_launch.argtypes = [vp] + [C.POINTER(C.c_int32)] * 6
     L.mi355_lbfgs_last_arithmetic.argtypes = [vp, C.POINTER(C.c_int32)]

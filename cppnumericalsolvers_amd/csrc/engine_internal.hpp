@@ -166,6 +166,12 @@ int dispatch_lbfgsb_e(mi355_lbfgs_ctx* ctx, int E, int objective, int linesearch
 // More-Thuente, Rosenbrock / DiagQuadratic, m <= 8 (n <= 64) or m <= 5 (n <= 128); 32 lanes for m = 9, 10 (n <= 64)
 int dispatch_lbfgsb_fast(mi355_lbfgs_ctx* ctx, int W, int E, int objective, const LbfgsbArgs& args, hipStream_t stream);
 int dispatch_lbfgsb_fast_w32(mi355_lbfgs_ctx* ctx, int E, int objective, const LbfgsbArgs& args, hipStream_t stream);
+// One box per problem (args.box_stride != 0; mi355_lbfgsb_minimize_batch_boxes): the OwnBox instantiations, a bounded set.
+// dispatch_lbfgsb_own_box.hip — reference-order kernel, More-Thuente, 16 lanes, E = 1, 2, 4 (n <= 64): m <= 8 on Rosenbrock /
+// DiagQuadratic, m <= 5 on SquaredErrorRidge.  dispatch_lbfgsb_fast_own_box.hip — relaxed kernel, Rosenbrock /
+// DiagQuadratic, E = 1, 2 (n <= 32, the unstaged form), m <= 8.  The entry point has refused everything else.
+int dispatch_lbfgsb_own_box(mi355_lbfgs_ctx* ctx, int E, int objective, const LbfgsbArgs& args, hipStream_t stream);
+int dispatch_lbfgsb_fast_own_box(mi355_lbfgs_ctx* ctx, int E, int objective, const LbfgsbArgs& args, hipStream_t stream);
 // The lean solve kernels (dispatch_lean.hip): lbfgs_solve_kernel<W, 4, RosenbrockFullObjective, 6 | 10, ..., ArithFma,
 // LeanOptions> for W = 8, 16 — the shapes of the flagship batches — with the options of a plain First-mode solve fixed at
 // compile time (lbfgs_kernel.hpp, LeanOptions).  launch_solve_rosenbrock_full picks them when lean_options_hold(args).
@@ -639,12 +645,12 @@ int dispatch_e(mi355_lbfgs_ctx* ctx, int E, int objective, int mr, const SolveAr
 }
 
 
-template <int E, class Obj, int M, int LS = MI355_LS_MORE_THUENTE, class OUTER = NoOuterLoop, int W = 16>
+template <int E, class Obj, int M, int LS = MI355_LS_MORE_THUENTE, class OUTER = NoOuterLoop, int W = 16, bool OwnBox = false>
 int launch_lbfgsb(mi355_lbfgs_ctx* ctx, LbfgsbArgs args, hipStream_t stream, const typename OUTER::Args& outer_args = {}) {
   constexpr int kSegs = kWave / W;
   const int lds = (Obj::shared_lds_doubles() + kSegs * lbfgsb_lds_doubles_per_problem<M>(W * E, Obj::kLdsDoubles)) *
                   static_cast<int>(sizeof(double));
-  auto kern = lbfgsb_solve_kernel<E, Obj, M, LS, OUTER, W>;
+  auto kern = lbfgsb_solve_kernel<E, Obj, M, LS, OUTER, W, OwnBox>;
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   int per_cu = 0;
   HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kWave, lds));

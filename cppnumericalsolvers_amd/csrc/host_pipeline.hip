@@ -932,6 +932,62 @@ int mi355_lbfgsb_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_des
   return rc;
 }
 
+// One box per problem, HOST rows [B][box_stride].  The rows of a chunk travel with that chunk: run_host_batch hands the
+// chunks to `solve` in batch order, so the chunk that starts at row `done` takes rows done .. done + bc.  Two device slots,
+// used alternately like the staging slots; the copies are ordered on the solve stream, behind the launch that last read
+// the slot.
+int mi355_lbfgsb_minimize_batch_boxes_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, const double* lower,
+                                           const double* upper, int64_t box_stride, int64_t B, const double* x0,
+                                           double* x_out, double* f_out, double* g_out,
+                                           mi355_lbfgs_progress* progress_out) {
+  if (!ctx || !desc) return fail(MI355_ERR_INVALID_ARGUMENT, "null context / desc");
+  if (B < 0) return fail(MI355_ERR_INVALID_ARGUMENT, "negative batch size");
+  if (desc->n < 1 || desc->n > MI355_LBFGS_MAX_N) return fail(MI355_ERR_INVALID_ARGUMENT, "n out of range [1, MI355_LBFGS_MAX_N]");
+  if (!lower || !upper)
+    return fail(MI355_ERR_INVALID_ARGUMENT, "per-problem bounds: lower and upper are required (the shared entry point "
+                                            "takes the default box)");
+  if (box_stride < desc->n) return fail(MI355_ERR_INVALID_ARGUMENT, "per-problem bounds: box_stride must be >= n");
+  for (int64_t b = 0; b < B; ++b)   // (see mi355_lbfgsb_minimize_batch_host; the padding of a row is not looked at)
+    for (int j = 0; j < desc->n; ++j)
+      if (lower[b * box_stride + j] != lower[b * box_stride + j] || upper[b * box_stride + j] != upper[b * box_stride + j])
+        return fail(MI355_ERR_INVALID_ARGUMENT, "NaN bound");
+  // validation, the refusals of what is not built, and B == 0: the device entry point's (nothing is launched)
+  {
+    const double* const nonnull = lower;  // never dereferenced at B = 0
+    const int rc0 = mi355_lbfgsb_minimize_batch_boxes(ctx, desc, nonnull, nonnull, box_stride, 0, nullptr, nullptr, nullptr,
+                                                      nullptr, nullptr, nullptr);
+    if (rc0 != MI355_OK || B == 0) return rc0;
+  }
+  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
+  MI355_ENTER_DEVICE(ctx);
+  double* rows_dev = nullptr;   // [2 slots][lower, upper][chunk][box_stride], allocated at the first chunk (the largest)
+  size_t slot_doubles = 0;
+  int64_t done = 0, chunk_index = 0;
+  const int rc = run_host_batch(
+      ctx, desc, B, x0, x_out, f_out, g_out, progress_out,
+      [&](const mi355_lbfgs_desc* dd, int64_t bc, const double* a, double* b, double* f, double* gg, mi355_lbfgs_progress* p,
+          hipStream_t st) {
+        const size_t rows = static_cast<size_t>(bc) * static_cast<size_t>(box_stride);
+        if (!rows_dev) {
+          slot_doubles = 2 * rows;
+          HIP_TRY(hipMalloc(reinterpret_cast<void**>(&rows_dev), 2 * slot_doubles * sizeof(double)));
+        }
+        if (2 * rows > slot_doubles) return fail(MI355_ERR_HIP, "lbfgsb host batch: a later chunk is larger than the first");
+        double* const lo_dev = rows_dev + (chunk_index & 1) * slot_doubles;
+        double* const hi_dev = lo_dev + rows;
+        HIP_TRY(hipMemcpyAsync(lo_dev, lower + done * box_stride, rows * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(hi_dev, upper + done * box_stride, rows * sizeof(double), hipMemcpyHostToDevice, st));
+        done += bc;
+        ++chunk_index;
+        return mi355_lbfgsb_minimize_batch_boxes(ctx, dd, lo_dev, hi_dev, box_stride, bc, a, b, f, gg, p, st);
+      });
+  if (rows_dev) {
+    (void)hipDeviceSynchronize();
+    (void)hipFree(rows_dev);
+  }
+  return rc;
+}
+
 }  // extern "C"
 
 // ---- host-pointer entry points of TrustRegionNewton, NelderMead, NewtonDescent and the first-order solvers ----------

@@ -8,13 +8,13 @@
 
 namespace mi355 {
 
-template <int E, class Obj, int M>
+template <int E, class Obj, int M, bool OwnBox = false>
 int launch_lbfgsb_fast(mi355_lbfgs_ctx* ctx, LbfgsbArgs args, hipStream_t stream) {
   constexpr int W = lbfgsb_fast_lanes(M), kSegs = kWave / W;
   const int lds = (Obj::shared_lds_doubles() + kSegs * lbfgsb_fast_lds_doubles_per_problem<M>(W * E, Obj::kLdsDoubles) +
                    lbfgsb_fast_shared_tail_doubles(W * E)) * static_cast<int>(sizeof(double));
   if (lds > 160 * 1024) return fail(MI355_ERR_INVALID_ARGUMENT, "history / objective data do not fit LDS");
-  auto kern = lbfgsb_fast_kernel<E, Obj, M>;
+  auto kern = lbfgsb_fast_kernel<E, Obj, M, lbfgsb_fast_lanes(M), OwnBox>;
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   int per_cu = 0;
   HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kWave, lds));

@@ -170,7 +170,9 @@ __device__ __forceinline__ double fast_solve_k(double (&row)[K2], double rv, int
   return rv * dinv;
 }
 
-template <int E, class Obj, int M, int W = lbfgsb_fast_lanes(M)>
+// OwnBox: one box per problem, read at the fetch point (see lbfgsb_solve_kernel); the unstaged form only — the staged
+// form keeps ONE box per workgroup in LDS and would need one per segment.
+template <int E, class Obj, int M, int W = lbfgsb_fast_lanes(M), bool OwnBox = false>
 __global__ __launch_bounds__(64, (M > 5 || E >= 8) ? 1 : 2) void lbfgsb_fast_kernel(const LbfgsbArgs args) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   static_assert(W == lbfgsb_fast_lanes(M), "segment width follows from the capacity");
@@ -201,6 +203,7 @@ __global__ __launch_bounds__(64, (M > 5 || E >= 8) ? 1 : 2) void lbfgsb_fast_ker
   double* const past_f = ubuf + W;
   double* const ypinv = past_f + MI355_LBFGS_MAX_PAST;    // [W]: pivot reciprocals of the Y block (fast_factor_mm)
   constexpr bool kStaged = lbfgsb_fast_staged(P);
+  static_assert(!(OwnBox && kStaged), "per-problem boxes are built for the unstaged form (box in registers)");
   double* const stage = ypinv + W;                        // kStaged: [3][P] = x at the start of the step, xcur, gcur
   const double* const mycol = Wc + ra * PITCH;
 
@@ -228,8 +231,12 @@ __global__ __launch_bounds__(64, (M > 5 || E >= 8) ? 1 : 2) void lbfgsb_fast_ker
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       const int j = sl * E + e;
-      lo_reg[e] = (j < n) ? args.lower[j] : 0.0;
-      hi_reg[e] = (j < n) ? args.upper[j] : 0.0;
+      if constexpr (OwnBox) {
+        lo_reg[e] = hi_reg[e] = 0.0;  // (read at the fetch point)
+      } else {
+        lo_reg[e] = (j < n) ? args.lower[j] : 0.0;
+        hi_reg[e] = (j < n) ? args.upper[j] : 0.0;
+      }
     }
   }
   auto lo_at = [&](int e) -> double {
@@ -322,6 +329,18 @@ __global__ __launch_bounds__(64, (M > 5 || E >= 8) ? 1 : 2) void lbfgsb_fast_ker
         for (int e = 0; e < E; ++e) {
           const int j = sl * E + e;
           x[e] = (j < n) ? x0p[prob * n + j] : 0.0;
+        }
+      }
+      if constexpr (OwnBox) {  // the problem's own box (row `prob` after the map, like x0)
+        const KernargLbfgsbArgs cb = cold_lbfgsb_args();
+        const long long row = prob * cb->box_stride;
+        const double* const lop = cb->lower + row;
+        const double* const hip = cb->upper + row;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          const int j = sl * E + e;
+          lo_reg[e] = (j < n) ? lop[j] : 0.0;
+          hi_reg[e] = (j < n) ? hip[j] : 0.0;
         }
       }
       obj.begin_problem(ca->per_problem, prob, ca->per_problem_stride, sl);

@@ -51,10 +51,21 @@ namespace mi355 {
 
 struct LbfgsbArgs {
   SolveArgs s;            // shared fields (x0, outputs, objective, stop, queue, B, n; s.m = history size)
-  const double* lower;    // device, n doubles (shared by the batch)
+  const double* lower;    // device, n doubles (shared by the batch) — or, box_stride != 0, one row per problem
   const double* upper;
   int relaxed;            // host side only: the relaxed-algebra kernel (lbfgsb_fast_kernel.hpp) was selected
+  long long box_stride;   // 0: one box shared by the batch; otherwise doubles per row of lower / upper (>= n), and the
+                          // launch takes the OwnBox instantiation of its kernel
 };
+
+// The kernel's own by-value LbfgsbArgs in the kernarg segment (it is the first kernel argument), for the fields an OwnBox
+// kernel needs once per problem: see cold_args (lbfgs_kernel.hpp).
+typedef const __attribute__((address_space(4))) LbfgsbArgs* KernargLbfgsbArgs;
+__device__ __forceinline__ KernargLbfgsbArgs cold_lbfgsb_args() {
+  unsigned long long p = reinterpret_cast<unsigned long long>(__builtin_amdgcn_kernarg_segment_ptr());
+  asm volatile("" : "+s"(p));
+  return reinterpret_cast<KernargLbfgsbArgs>(p);
+}
 
 constexpr int kRowNewBcast = 0x150;  // DPP: lane N of each 16-lane row to the whole row
 constexpr int kRowRor8 = 0x128;      // DPP row_ror:8: lane l <- lane l^8 of its 16-lane row
@@ -310,7 +321,10 @@ __host__ __device__ inline int lbfgsb_lds_doubles_per_problem(int P, int objecti
 // OUTER: as for lbfgs_solve_kernel (NoOuterLoop, or the augmented-Lagrangian loop around the solves of a problem)
 // W: lanes per problem.  16 (one DPP row) serves 2M <= 16 rows of the compact representation; 32 lanes serve M = 10
 // (the broadcasts and the last butterfly level cross the two rows of the segment with v_permlane16_swap).
-template <int E, class Obj, int M, int LS = MI355_LS_MORE_THUENTE, class OUTER = NoOuterLoop, int W = 16>
+// OwnBox: every problem has its own box (args.box_stride doubles per row).  The box is then read where the start point is
+// read, once per fetched problem, instead of once per wavefront; everything that uses it is the same code.  A template
+// switch and not a run-time one: the shared-box kernels keep their instructions and registers.
+template <int E, class Obj, int M, int LS = MI355_LS_MORE_THUENTE, class OUTER = NoOuterLoop, int W = 16, bool OwnBox = false>
 // (two wavefronts per SIMD asked for where the kernel fits 256 registers — one or two coordinates per lane, m <= 5:
 // without the hint the allocator hoists the
 // per-column scale / index of W out of the iteration and ends at 272)
@@ -356,8 +370,12 @@ __global__ __launch_bounds__(64, (E >= 4 || M > 5 || W > 16) ? 1 : 2) void lbfgs
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     const int j = sl * E + e;
-    lo[e] = (j < n) ? args.lower[j] : 0.0;
-    hi[e] = (j < n) ? args.upper[j] : 0.0;
+    if constexpr (OwnBox) {
+      lo[e] = hi[e] = 0.0;  // (read at the fetch point)
+    } else {
+      lo[e] = (j < n) ? args.lower[j] : 0.0;
+      hi[e] = (j < n) ? args.upper[j] : 0.0;
+    }
   }
   auto clip = [&](const double (&v)[E], double (&out)[E]) {  // cwiseMin(upper).cwiseMax(lower)
 #pragma unroll
@@ -457,6 +475,18 @@ __global__ __launch_bounds__(64, (E >= 4 || M > 5 || W > 16) ? 1 : 2) void lbfgs
         for (int e = 0; e < E; ++e) {
           const int j = sl * E + e;
           x[e] = (j < n) ? x0p[prob * n + j] : 0.0;
+        }
+      }
+      if constexpr (OwnBox) {  // ---- and the problem's own box (row `prob` after the map, like x0) ----
+        const KernargLbfgsbArgs cb = cold_lbfgsb_args();
+        const long long row = prob * cb->box_stride;
+        const double* const lop = cb->lower + row;
+        const double* const hip = cb->upper + row;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          const int j = sl * E + e;
+          lo[e] = (j < n) ? lop[j] : 0.0;
+          hi[e] = (j < n) ? hip[j] : 0.0;
         }
       }
       obj.begin_problem(ca->per_problem, prob, ca->per_problem_stride, sl);

@@ -798,10 +798,18 @@ int ensure_bounds(mi355_lbfgs_ctx* ctx, size_t doubles) {
 
 }  // namespace
 
-extern "C" int mi355_lbfgsb_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, const double* lower,
-                                           const double* upper, int64_t B, const double* x0, double* x_out,
-                                           double* f_out, double* g_out, mi355_lbfgs_progress* progress_out,
-                                           void* stream_) {
+namespace {
+// what is built for one box per problem (dispatch_lbfgsb_own_box.hip, dispatch_lbfgsb_fast_own_box.hip)
+const char kOwnBoxRange[] =
+    "; per-problem bounds are built for the More-Thuente line search, n <= 64, on Rosenbrock / DiagQuadratic with m <= 8 and "
+    "SquaredErrorRidge with m <= 5, MI355_ARITH_FMA (relaxed algebra) on Rosenbrock / DiagQuadratic with n <= 32";
+int own_box_refusal(const char* what) { return fail(MI355_ERR_UNSUPPORTED, std::string(what) + kOwnBoxRange); }
+
+// box_stride == 0: lower / upper are one box of n doubles (or both NULL: the default box).  Otherwise one row of box_stride
+// doubles per problem (mi355_lbfgsb_minimize_batch_boxes).
+int lbfgsb_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, const double* lower, const double* upper,
+                          int64_t box_stride, bool own_box, int64_t B, const double* x0, double* x_out, double* f_out,
+                          double* g_out, mi355_lbfgs_progress* progress_out, void* stream_) {
   int rc = validate(ctx, desc, B);
   if (rc != MI355_OK) return rc;
   if (desc->m > 10) return fail(MI355_ERR_UNSUPPORTED, "L-BFGS-B is built for m <= 10 (5 is the reference default)");
@@ -810,8 +818,24 @@ extern "C" int mi355_lbfgsb_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbf
     return fail(MI355_ERR_UNSUPPORTED, "Lbfgsb has no preconditioned (Second-mode) path (lbfgsb.h:48-49)");
   if (desc->lanes_per_problem != 0 || desc->elems_per_lane != 0 || desc->history_placement != 0)
     return fail(MI355_ERR_INVALID_ARGUMENT, "L-BFGS-B chooses its own mapping: leave the mapping fields 0");
-  if ((lower == nullptr) != (upper == nullptr))
+  if (own_box) {
+    if (!lower || !upper)
+      return fail(MI355_ERR_INVALID_ARGUMENT, "per-problem bounds: lower and upper are required (the shared entry point "
+                                              "takes the default box)");
+    if (box_stride < desc->n) return fail(MI355_ERR_INVALID_ARGUMENT, "per-problem bounds: box_stride must be >= n");
+    // the built range, before anything is uploaded or launched
+    const bool plain = desc->objective == MI355_OBJ_ROSENBROCK || desc->objective == MI355_OBJ_DIAG_QUADRATIC;
+    if (desc->objective >= MI355_OBJ_USER_FIRST) return own_box_refusal("user objectives have no per-problem-bounds kernels");
+    if (!plain && desc->objective != MI355_OBJ_SQUARED_ERROR_RIDGE)
+      return own_box_refusal("this objective (the augmented-Lagrangian composite included) has no per-problem-bounds kernels");
+    if (desc->linesearch != MI355_LS_MORE_THUENTE) return own_box_refusal("the Hager-Zhang line search is not built");
+    if (desc->n > 64) return own_box_refusal("n > 64 is not built");
+    if (desc->m > (plain ? 8 : 5)) return own_box_refusal(plain ? "m = 9, 10 are not built" : "m > 5 on SquaredErrorRidge is not built");
+    if (desc->arithmetic == MI355_ARITH_FMA && !(plain && desc->n <= 32))
+      return own_box_refusal("MI355_ARITH_FMA outside the relaxed range");
+  } else if ((lower == nullptr) != (upper == nullptr)) {
     return fail(MI355_ERR_INVALID_ARGUMENT, "lower and upper must both be given or both be NULL");
+  }
   if (B == 0) return MI355_OK;
   if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -837,6 +861,9 @@ extern "C" int mi355_lbfgsb_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbf
                 "MI355_ARITH_FMA (relaxed algebra) for L-BFGS-B is built for the More-Thuente line search on the Rosenbrock "
                 "/ DiagQuadratic objectives and user functors with an eval_fma: m <= 10 (n <= 64), m <= 5 (n <= 128)");
   bool use_fast = fast_built && desc->arithmetic != MI355_ARITH_EXACT;
+  // one box per problem: the relaxed kernel exists in its unstaged form only (n <= 32), so MI355_ARITH_DEFAULT takes the
+  // reference-order kernel at 32 < n <= 64 — where the shared entry's default is the relaxed one
+  if (own_box && n > 32) use_fast = false;
   // MI355_ARITH_DEFAULT stays inside the envelope where the relaxed algebra is pinned to 1e-6 of the reference binary
   // (tests/test_relaxed_envelope.py): a diagonal quadratic whose spectrum spreads over more than
   // MI355_LBFGSB_RELAXED_MAX_SPREAD takes the reference-order kernel; MI355_ARITH_FMA still forces the relaxed one.
@@ -887,6 +914,10 @@ extern "C" int mi355_lbfgsb_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbf
   args.lower = lower;
   args.upper = upper;
   args.relaxed = use_fast ? 1 : 0;
+  args.box_stride = own_box ? box_stride : 0;
+  if (own_box)
+    return use_fast ? dispatch_lbfgsb_fast_own_box(ctx, E, desc->objective, args, stream)
+                    : dispatch_lbfgsb_own_box(ctx, E, desc->objective, args, stream);
   if (desc->objective >= MI355_OBJ_USER_FIRST) {
     const auto fn = user_solver_fn<kUserLbfgsb>(desc->objective);
     if (!fn) return fail(MI355_ERR_UNSUPPORTED, "no user objective with this id is compiled into this library for L-BFGS-B");
@@ -904,6 +935,21 @@ extern "C" int mi355_lbfgsb_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbf
   if (use_fast) return dispatch_lbfgsb_fast(ctx, two_rows ? 32 : 16, E, desc->objective, args, stream);
   if (two_rows) return dispatch_lbfgsb_w32(ctx, desc->objective, desc->linesearch, args, stream);
   return dispatch_lbfgsb_e(ctx, E, desc->objective, desc->linesearch, args, stream);
+}
+}  // namespace
+
+extern "C" int mi355_lbfgsb_minimize_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, const double* lower,
+                                           const double* upper, int64_t B, const double* x0, double* x_out,
+                                           double* f_out, double* g_out, mi355_lbfgs_progress* progress_out,
+                                           void* stream_) {
+  return lbfgsb_minimize_batch(ctx, desc, lower, upper, 0, false, B, x0, x_out, f_out, g_out, progress_out, stream_);
+}
+
+extern "C" int mi355_lbfgsb_minimize_batch_boxes(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, const double* lower,
+                                                 const double* upper, int64_t box_stride, int64_t B, const double* x0,
+                                                 double* x_out, double* f_out, double* g_out,
+                                                 mi355_lbfgs_progress* progress_out, void* stream_) {
+  return lbfgsb_minimize_batch(ctx, desc, lower, upper, box_stride, true, B, x0, x_out, f_out, g_out, progress_out, stream_);
 }
 
 extern "C" {

@@ -562,9 +562,11 @@ class BatchedLbfgsb(BatchedLbfgs):
     """Batched `Lbfgsb<F, m>` (reference solver/lbfgsb.h, default m = 5; built for m <= 10): box-constrained L-BFGS-B.
 
     `SetBounds(lower, upper)` mirrors the reference (lbfgsb.h:89-93); without it the box is
-    unbounded.  stopping_progress defaults to what a default-constructed reference Lbfgsb uses
-    (f_delta = 2.22e-9 relative on top of the default preset); its gradient_norm is the
-    projected-gradient tolerance."""
+    unbounded.  `SetBoundsPerProblem(lower, upper)` gives every problem of the batch its own box ([B, n] rows: what B
+    reference solvers with B SetBounds calls solve; see mi355_lbfgsb_minimize_batch_boxes for the built range — at
+    32 < n <= 64 arithmetic="default" is the reference-order kernel there).  stopping_progress defaults to what a
+    default-constructed reference Lbfgsb uses (f_delta = 2.22e-9 relative on top of the default preset); its
+    gradient_norm is the projected-gradient tolerance."""
 
     def __init__(self, m=5, stopping_progress=None, device=0, context=None, linesearch="more_thuente",
                  arithmetic="default"):
@@ -576,6 +578,33 @@ class BatchedLbfgsb(BatchedLbfgs):
                          device=device, context=context)
         self._lower = None
         self._upper = None
+        self._rows = None    # SetBoundsPerProblem: (lower, upper), [B, n] each; in force while no shared box is set
+
+    def SetBoundsPerProblem(self, lower, upper):
+        """One box per problem: `lower` / `upper` are [B, n] float64 numpy arrays or tensors on the solver's device.
+        `minimize` / `minimize_host` then check B and n against x0.  A later `SetBounds` returns to one shared box."""
+        torch = self._torch
+        rows = []
+        for t in (lower, upper):
+            if not torch.is_tensor(t):
+                t = torch.as_tensor(np.ascontiguousarray(t, dtype=np.float64))
+            if t.dtype != torch.float64 or t.dim() != 2:
+                raise ValueError("per-problem bounds must be [B, n] float64 arrays")
+            if bool(torch.isnan(t).any()):
+                raise ValueError("NaN bound (the breakpoint order of the Cauchy search would be undefined, as in the reference)")
+            rows.append(t.to(self.device).contiguous())
+        if rows[0].shape != rows[1].shape:
+            raise ValueError("lower is %s, upper is %s" % (tuple(rows[0].shape), tuple(rows[1].shape)))
+        self._rows = tuple(rows)
+        self._lower = self._upper = None
+
+    def _own_boxes(self, B, n):
+        """The rows in force for a [B, n] batch, or None under a shared (or the default) box."""
+        if self._rows is None or self._lower is not None:
+            return None
+        if tuple(self._rows[0].shape) != (B, n):
+            raise ValueError("per-problem bounds are %s, x0 is %s" % (tuple(self._rows[0].shape), (B, n)))
+        return self._rows
 
     def SetBounds(self, lower, upper):
         if np.isnan(np.asarray(lower, dtype=np.float64)).any() or np.isnan(np.asarray(upper, dtype=np.float64)).any():
@@ -602,6 +631,14 @@ class BatchedLbfgsb(BatchedLbfgs):
         if trace is not None:
             self._trace_keepalive = trace
             d.trace = trace.c_pointer()
+        rows = self._own_boxes(B, n)
+        if rows is not None:
+            capi.check(self.ctx._lib.mi355_lbfgsb_minimize_batch_boxes(
+                self.ctx.handle, C.byref(d), rows[0].data_ptr(), rows[1].data_ptr(), n,
+                B, x0.data_ptr(), x.data_ptr(), f.data_ptr(),
+                g.data_ptr() if g is not None else None, prog.data_ptr() if prog is not None else None,
+                self._stream()))
+            return x, f, g, prog
         capi.check(self.ctx._lib.mi355_lbfgsb_minimize_batch(
             self.ctx.handle, C.byref(d),
             self._lower.data_ptr() if self._lower is not None else None,
@@ -619,6 +656,16 @@ class BatchedLbfgsb(BatchedLbfgs):
         f = np.empty(B)
         prog = np.zeros(B, dtype=capi.PROGRESS_DTYPE)
         d = self._desc(objective, n)
+        rows = self._own_boxes(B, n)
+        if rows is not None:
+            if per_problem is not None:
+                pp = np.ascontiguousarray(per_problem, dtype=np.float64)
+                d = self._desc(objective, n, pp.ctypes.data, pp.shape[1])
+            lo, hi = (np.ascontiguousarray(t.cpu().numpy()) for t in rows)
+            capi.check(self.ctx._lib.mi355_lbfgsb_minimize_batch_boxes_host(
+                self.ctx.handle, C.byref(d), lo.ctypes.data, hi.ctypes.data, n, B, x0.ctypes.data, x.ctypes.data,
+                f.ctypes.data, g.ctypes.data, prog.ctypes.data))
+            return x, f, g, prog
         lo = self._lower.cpu().numpy() if self._lower is not None else None
         hi = self._upper.cpu().numpy() if self._upper is not None else None
         capi.check(self.ctx._lib.mi355_lbfgsb_minimize_batch_host(
@@ -696,6 +743,9 @@ class DeviceGroup:
 
     def minimize_host_lbfgsb(self, solver, objective, x0, lower=None, upper=None, per_problem=None):
         """mi355_lbfgsb_group_minimize_batch_host: `solver` a BatchedLbfgsb (m / stopping / arithmetic)."""
+        if getattr(solver, "_rows", None) is not None and solver._lower is None:
+            raise capi.EngineError(capi.ERR_UNSUPPORTED, "per-problem bounds (SetBoundsPerProblem) are not built for device "
+                                                         "groups: one context, n <= 64")
         lo = np.ascontiguousarray(lower, dtype=np.float64) if lower is not None else None
         hi = np.ascontiguousarray(upper, dtype=np.float64) if upper is not None else None
         return self._host_call("mi355_lbfgsb_group_minimize_batch_host", solver, objective, x0, per_problem,

@@ -4,7 +4,7 @@
 // `SetBounds(lower, upper)` (:89-93), `Minimize` (:247-292; stops on the PROJECTED gradient norm),
 // a default constructor that adds the relative f-delta test (:84-87) and the inherited constructor
 // taking an explicit `Progress` (:74).  The solve runs in `lbfgsb_solve_kernel` behind
-// `mi355_lbfgsb_minimize_batch_host` (include/mi355_lbfgs.h).  New: MinimizeBatch.
+// `mi355_lbfgsb_minimize_batch_host` (include/mi355_lbfgs.h).  New: MinimizeBatch, also with one box per state.
 #ifndef INCLUDE_CPPOPTLIB_SOLVER_LBFGSB_H_
 #define INCLUDE_CPPOPTLIB_SOLVER_LBFGSB_H_
 
@@ -114,6 +114,43 @@ class Lbfgsb : public Solver<FunctionType, cppoptlib::function::FunctionState<ty
     std::vector<double> x(x0.size()), g(x0.size()), f(static_cast<size_t>(B));
     std::vector<mi355_lbfgs_progress> prog(static_cast<size_t>(B));
     MinimizeBatchRaw(function, n, B, x0.data(), x.data(), f.data(), g.data(), prog.data());
+    return cppoptlib::mi355::UnpackResults<StateType, ProgressType, VectorType>(n, B, x, f, g, prog);
+  }
+
+  // One box per start state (what states.size() reference solvers with their own SetBounds solve), over
+  // mi355_lbfgsb_minimize_batch_boxes_host; see there for the shapes it is built for.  The object's own SetBounds box is
+  // not consulted.
+  std::vector<std::tuple<StateType, ProgressType>> MinimizeBatch(const FunctionType& function,
+                                                                 const std::vector<StateType>& states,
+                                                                 const std::vector<VectorType>& lower,
+                                                                 const std::vector<VectorType>& upper) {
+    const int64_t B = static_cast<int64_t>(states.size());
+    if (lower.size() != states.size() || upper.size() != states.size())
+      cppoptlib::mi355::Fail("MinimizeBatch: one lower and one upper bound per start state");
+    if (B == 0) return {};
+    const int n = static_cast<int>(states[0].x.size());
+    std::vector<double> lo(static_cast<size_t>(B) * n), hi(lo.size());
+    for (size_t b = 0; b < static_cast<size_t>(B); ++b) {
+      if (static_cast<int>(lower[b].size()) != n || static_cast<int>(upper[b].size()) != n)
+        cppoptlib::mi355::Fail("MinimizeBatch: bound dimension mismatch");
+      for (int j = 0; j < n; ++j) {
+        const double l = lower[b][j], u = upper[b][j];
+        if (l != l || u != u) cppoptlib::mi355::Fail("MinimizeBatch: NaN bound");
+        lo[b * n + j] = l;
+        hi[b * n + j] = u;
+      }
+    }
+    if (!ctx_) ctx_ = cppoptlib::mi355::Context::Default();
+    const std::vector<double> x0 = cppoptlib::mi355::PackStates(states, n);
+    std::vector<double> x(x0.size()), g(x0.size()), f(static_cast<size_t>(B));
+    std::vector<mi355_lbfgs_progress> prog(static_cast<size_t>(B));
+    std::vector<double> params, rows;
+    mi355_lbfgs_desc d = Desc(function, n, &params, nullptr);
+    d.per_problem_stride = cppoptlib::mi355::PackPerProblem(function, B, &rows);
+    d.per_problem_data = rows.empty() ? nullptr : rows.data();
+    cppoptlib::mi355::Check(mi355_lbfgsb_minimize_batch_boxes_host(ctx_->get(), &d, lo.data(), hi.data(), n, B, x0.data(),
+                                                                   x.data(), f.data(), g.data(), prog.data()),
+                            "mi355_lbfgsb_minimize_batch_boxes_host");
     return cppoptlib::mi355::UnpackResults<StateType, ProgressType, VectorType>(n, B, x, f, g, prog);
   }
 

@@ -347,6 +347,31 @@ int mi355_lbfgsb_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_des
                                      const double* upper, int64_t B, const double* x0, double* x_out,
                                      double* f_out, double* g_out, mi355_lbfgs_progress* progress_out);
 
+/* The same solver with ONE BOX PER PROBLEM: what B Lbfgsb objects with B SetBounds calls (lbfgsb.h:89-93) solve.
+ * `lower` / `upper`: [B][box_stride] doubles, box_stride >= n; row b is the box of problem b (the padding of a row is not
+ * read).  Both are required — a NULL pointer or box_stride < n is MI355_ERR_INVALID_ARGUMENT; the default box is asked
+ * for through mi355_lbfgsb_minimize_batch.  lower > upper is not checked, as there.  All other validation, the trace,
+ * desc->count_dev and the last_launch / last_kernel_ms records are those of mi355_lbfgsb_minimize_batch.
+ * Built range (a bounded set of kernels that read the box with the start point of every problem they fetch; the
+ * arithmetic downstream is that of the shared-box kernels, bit for bit): the More-Thuente search and n <= 64 on
+ * Rosenbrock / DiagQuadratic with m <= 8 and on SquaredErrorRidge with m <= 5; the relaxed-algebra kernels
+ * (MI355_ARITH_FMA) on Rosenbrock / DiagQuadratic with n <= 32, m <= 8.  MI355_ARITH_DEFAULT takes the relaxed kernel
+ * where one is built (under the MI355_LBFGSB_RELAXED_MAX_SPREAD rule of the shared entry) and the reference-order kernel
+ * otherwise — so at 32 < n <= 64 the default here is the reference-order kernel where the shared entry's default is the
+ * relaxed one; mi355_lbfgs_last_arithmetic reports what ran.  Hager-Zhang, m = 9 and 10, n > 64, user objectives, the
+ * augmented-Lagrangian composite and MI355_ARITH_FMA outside the relaxed range return MI355_ERR_UNSUPPORTED and launch
+ * nothing.  Device pointers, asynchronous on `stream`. */
+int mi355_lbfgsb_minimize_batch_boxes(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, const double* lower,
+                                      const double* upper, int64_t box_stride, int64_t B, const double* x0,
+                                      double* x_out, double* f_out, double* g_out, mi355_lbfgs_progress* progress_out,
+                                      void* stream);
+/* Same with HOST pointers (rows included), synchronous.  A NaN in any row is refused ("NaN bound").  A batch that goes
+ * through the staging slots in chunks takes each chunk's rows along with that chunk. */
+int mi355_lbfgsb_minimize_batch_boxes_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, const double* lower,
+                                           const double* upper, int64_t box_stride, int64_t B, const double* x0,
+                                           double* x_out, double* f_out, double* g_out,
+                                           mi355_lbfgs_progress* progress_out);
+
 /* Dense BFGS: replaces cppoptlib::solver::Bfgs<FunctionType, LineSearch>::Minimize (solver/bfgs.h:65-137 under
  * Solver::Minimize, solver/solver.h:181-224) for B problems at once — same driver, line searches
  * (desc->linesearch) and stopping tests as mi355_lbfgs_minimize_batch, with an explicit n x n inverse-
