@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = [
     "mi355_lbfgs_group_minimize_batch_host", "mi355_lbfgs_group_allreduce_flags",
     "mi355_lbfgsb_group_minimize_batch_host", "mi355_bfgs_group_minimize_batch_host",
     "mi355_lbfgs_group_minimize_batch", "mi355_lbfgsb_group_minimize_batch",
+    "mi355_lbfgs_minimize_batch_f32", "mi355_lbfgs_minimize_batch_f32_host", "mi355_lbfgs_eval_batch_f32",
 ]
 
 
@@ -270,6 +271,9 @@ def _bind(L):
     L.mi355_lbfgs_default_stop.argtypes = [C.c_int, C.POINTER(Stop)]
     L.mi355_lbfgs_minimize_batch.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mi355_lbfgs_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp]
+    L.mi355_lbfgs_minimize_batch_f32.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.mi355_lbfgs_minimize_batch_f32_host.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp]
+    L.mi355_lbfgs_eval_batch_f32.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp]
     L.mi355_bfgs_minimize_batch.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mi355_bfgs_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp]
     L.mi355_trust_region_default_config.argtypes = [C.POINTER(TrustRegionConfig)]

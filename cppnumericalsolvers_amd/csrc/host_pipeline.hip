@@ -1069,3 +1069,67 @@ extern "C" int mi355_conjugated_gradient_descent_minimize_batch_host(mi355_lbfgs
                                       return mi355_conjugated_gradient_descent_minimize_batch(ctx, dd, config, rest...);
                                     });
 }
+
+// ---- float Lbfgs with HOST arrays (mi355_lbfgs_minimize_batch_f32) ------------------------------------------------------
+// The same pinned staging slot and chunking by MI355_HOST_STAGE_BYTES as run_host_batch, with float rows; the chunks run
+// one after the other on the context's solve stream (no overlap of a chunk's copies with the next chunk's solve).  The
+// double path above is untouched.
+extern "C" int mi355_lbfgs_minimize_batch_f32(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const float* x0,
+                                              float* x_out, float* f_out, float* g_out,
+                                              mi355_lbfgs_progress* progress_out, void* stream);
+extern "C" int mi355_lbfgs_minimize_batch_f32_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B,
+                                                   const float* x0, float* x_out, float* f_out, float* g_out,
+                                                   mi355_lbfgs_progress* progress_out) {
+  // the refusals and argument checks, before anything is staged (B = 0: nothing is launched)
+  int rc = mi355_lbfgs_minimize_batch_f32(ctx, desc, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (rc != MI355_OK) return rc;
+  if (B < 0) return fail(MI355_ERR_INVALID_ARGUMENT, "negative batch size");
+  if (B == 0) return MI355_OK;
+  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
+  MI355_ENTER_DEVICE(ctx);
+  const size_t n = static_cast<size_t>(desc->n);
+  auto al = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
+  const bool want_g = g_out != nullptr, want_p = progress_out != nullptr;
+  struct L32 { size_t x0, x, g, f, p, total; };
+  auto lay = [&](int64_t C) {
+    const size_t c = static_cast<size_t>(C);
+    L32 l;
+    l.x0 = 0;
+    l.x = al(c * n * sizeof(float));
+    l.g = l.x + al(c * n * sizeof(float));
+    l.f = l.g + (want_g ? al(c * n * sizeof(float)) : 0);
+    l.p = l.f + al(c * sizeof(float));
+    l.total = l.p + (want_p ? al(c * sizeof(mi355_lbfgs_progress)) : 0);
+    return l;
+  };
+  int64_t chunk = static_cast<int64_t>(stage_bytes_max() / (lay(1024).total / 1024 + 1));
+  if (chunk < 1) chunk = 1;
+  if (chunk >= 64) chunk &= ~int64_t(63);
+  if (chunk > B) chunk = B;
+  const L32 l = lay(chunk);
+  rc = ensure_stage(ctx, 0, l.total);
+  if (rc != MI355_OK) return rc;
+  auto& st = ctx->stage[0];
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    const int64_t bc = std::min(chunk, B - b0);
+    const size_t rows = static_cast<size_t>(bc) * n * sizeof(float);
+    parallel_memcpy(st.pinned + l.x0, x0 + b0 * n, rows);
+    HIP_TRY(hipMemcpyAsync(st.device + l.x0, st.pinned + l.x0, rows, hipMemcpyHostToDevice, ctx->stream_solve));
+    rc = mi355_lbfgs_minimize_batch_f32(ctx, desc, bc, reinterpret_cast<const float*>(st.device + l.x0),
+                                        reinterpret_cast<float*>(st.device + l.x), reinterpret_cast<float*>(st.device + l.f),
+                                        want_g ? reinterpret_cast<float*>(st.device + l.g) : nullptr,
+                                        want_p ? reinterpret_cast<mi355_lbfgs_progress*>(st.device + l.p) : nullptr,
+                                        ctx->stream_solve);
+    if (rc != MI355_OK) {
+      (void)hipDeviceSynchronize();
+      return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(st.pinned + l.x, st.device + l.x, l.total - l.x, hipMemcpyDeviceToHost, ctx->stream_solve));
+    HIP_TRY(hipStreamSynchronize(ctx->stream_solve));
+    parallel_memcpy(x_out + b0 * n, st.pinned + l.x, rows);
+    if (want_g) parallel_memcpy(g_out + b0 * n, st.pinned + l.g, rows);
+    std::memcpy(f_out + b0, st.pinned + l.f, static_cast<size_t>(bc) * sizeof(float));
+    if (want_p) std::memcpy(progress_out + b0, st.pinned + l.p, static_cast<size_t>(bc) * sizeof(mi355_lbfgs_progress));
+  }
+  return MI355_OK;
+}

@@ -5,6 +5,7 @@
 // Solver record and two lambdas per entry point hold what differs; the one difference in order is NelderMead's objective
 // check, which also runs before validate() (ObjectiveCheck).  No kernel lives here.
 #include "engine_internal.hpp"
+#include "lbfgs_f32_config.hpp"
 
 namespace {
 using namespace mi355;
@@ -367,3 +368,103 @@ int mi355_conjugated_gradient_descent_minimize_batch(mi355_lbfgs_ctx* ctx, const
 }
 
 }  // extern "C"
+
+// ---- Lbfgs<F, m, MoreThuente> with ScalarType = float (lbfgs_f32_kernel.hpp) ------------------------------------------
+// Opt-in: the fp64 entry points are untouched and a float function that does not ask for this path is still widened.
+namespace {
+
+int f32_refuse(const char* text) { return fail(MI355_ERR_UNSUPPORTED, std::string("Lbfgs float32") + text); }
+
+// Everything the float entry points check before the device is touched: the refusals (MI355_ERR_UNSUPPORTED, with the
+// reason), validate()'s argument checks, the lane mapping.
+int f32_check(const mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, int& W, int& E) {
+  if (!desc) return fail(MI355_ERR_INVALID_ARGUMENT, "null desc");
+  if (desc->objective != MI355_OBJ_ROSENBROCK && desc->objective != MI355_OBJ_DIAG_QUADRATIC)
+    return f32_refuse(" is built for the Rosenbrock and DiagQuadratic objectives (no user functors, ridge forms or composites)");
+  if (desc->n > MI355_LBFGS_MAX_N) return f32_refuse(" is built for n <= 256");
+  if (desc->per_problem_data != nullptr) return f32_refuse(" takes no per-problem data");
+  const int rc = validate(ctx, desc, B);
+  if (rc != MI355_OK) return rc;
+  if (desc->linesearch != MI355_LS_MORE_THUENTE) return f32_refuse(" is built with the More-Thuente line search only");
+  if (desc->arithmetic == MI355_ARITH_FMA) return f32_refuse(" is built for the exact arithmetic only (no MI355_ARITH_FMA)");
+  if (desc->history_placement == MI355_HISTORY_Y_IN_REGISTERS)
+    return f32_refuse(" keeps both halves of the history in LDS (no MI355_HISTORY_Y_IN_REGISTERS)");
+  if (desc->hessian_from_functor || desc->hessian_diagonal != nullptr || desc->hessian_condition_stop > 0.0)
+    return f32_refuse(" is built for First-mode functions (no hessian_from_functor, hessian_diagonal or hessian_condition_stop)");
+  if (desc->trace != nullptr) return f32_refuse(" records no per-iteration trace");
+  W = desc->lanes_per_problem;
+  E = desc->elems_per_lane;
+  if (W == 0 && E == 0) {
+    W = 8;
+    while (W < desc->n && W < 64) W <<= 1;
+  }
+  if (E == 0 && (W == 8 || W == 16 || W == 32 || W == 64)) E = (desc->n <= W) ? 1 : ((desc->n <= 2 * W) ? 2 : 4);
+  const bool built = ((W == 8 || W == 16 || W == 32 || W == 64) && E == 1) || (W == 64 && (E == 2 || E == 4));
+  if (!built || W * E < desc->n)
+    return f32_refuse(": the mapping must cover n with 8, 16, 32 or 64 lanes at one coordinate per lane, or 64 lanes at "
+                      "two or four");
+  return MI355_OK;
+}
+
+// the objective's parameters as floats (each double converted once), through the context's parameter blob
+int f32_upload_params(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int W, int E, hipStream_t stream) {
+  if (desc->n_params == 0) return MI355_OK;
+  std::vector<float> as_float(static_cast<size_t>(desc->n_params) + 1, 0.0f);   // (+ 1: room to round up to whole doubles)
+  for (int i = 0; i < desc->n_params; ++i) as_float[i] = static_cast<float>(desc->objective_params[i]);
+  std::vector<double>& h = ctx->params_host;
+  h.assign((static_cast<size_t>(desc->n_params) + 1) / 2, 0.0);
+  std::memcpy(h.data(), as_float.data(), h.size() * sizeof(double));
+  mi355_lbfgs_desc blob = *desc;
+  blob.objective_params = h.data();
+  blob.n_params = static_cast<int>(h.size());
+  return upload_params(ctx, &blob, W, E, stream);
+}
+
+}  // namespace
+
+extern "C" int mi355_lbfgs_minimize_batch_f32(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const float* x0,
+                                              float* x_out, float* f_out, float* g_out,
+                                              mi355_lbfgs_progress* progress_out, void* stream_) {
+  int W = 0, E = 0;
+  int rc = f32_check(ctx, desc, B, W, E);
+  if (rc != MI355_OK) return rc;
+  if (B == 0) return MI355_OK;
+  if (!x0 || !x_out || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0 / x_out / f_out");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MI355_ENTER_DEVICE(ctx);
+  rc = f32_upload_params(ctx, desc, W, E, stream);
+  if (rc != MI355_OK) return rc;
+  SolveArgs args;
+  std::memset(&args, 0, sizeof(args));
+  args.progress_out = progress_out;
+  args.B = B;
+  args.n = desc->n;
+  args.m = desc->m;
+  args.stop = desc->stop;
+  f32::LbfgsF32Args fa;
+  fa.x0 = x0;
+  fa.x_out = x_out;
+  fa.f_out = f_out;
+  fa.g_out = g_out;
+  fa.obj_params = reinterpret_cast<const float*>(ctx->params_dev);
+  fa.stop_x_delta = static_cast<float>(desc->stop.x_delta);
+  fa.stop_f_delta = static_cast<float>(desc->stop.f_delta);
+  fa.stop_gradient_norm = static_cast<float>(desc->stop.gradient_norm);
+  fa.stop_past_delta = static_cast<float>(desc->stop.past_delta);
+  return dispatch_lbfgs_f32(ctx, W, E, desc->objective, args, fa, stream);
+}
+
+extern "C" int mi355_lbfgs_eval_batch_f32(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const float* x,
+                                          float* f_out, float* g_out, void* stream_) {
+  int W = 0, E = 0;
+  int rc = f32_check(ctx, desc, B, W, E);
+  if (rc != MI355_OK) return rc;
+  if (B == 0) return MI355_OK;
+  if (!x || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x / f_out");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MI355_ENTER_DEVICE(ctx);
+  rc = f32_upload_params(ctx, desc, W, E, stream);
+  if (rc != MI355_OK) return rc;
+  return dispatch_eval_f32(W, E, desc->objective, x, f_out, g_out, reinterpret_cast<const float*>(ctx->params_dev), B,
+                           desc->n, stream);
+}

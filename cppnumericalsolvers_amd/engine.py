@@ -212,21 +212,40 @@ class Trace:
         return rec[idx], x, g
 
 
+def _float64_only(solver, dtype):
+    """The solvers other than BatchedLbfgs compute in float64 only."""
+    if dtype is not None and str(dtype) != "torch.float64":
+        raise ValueError("%s computes in float64 only: dtype=torch.float32 is built for BatchedLbfgs (its native float "
+                         "path); got dtype=%s" % (type(solver).__name__, dtype))
+
+
 class BatchedLbfgs:
     """Batched `Lbfgs<F, m>` — one problem per wavefront segment on the GPU.
 
     stopping_progress: capi.Stop (defaults to DefaultStoppingSolverProgress).
     m: history size (reference default 10).
     lanes_per_problem / elems_per_lane: optional explicit wavefront mapping.
+    dtype: torch.float64 (default: every computation in fp64) or torch.float32 — the native float path
+        (mi355_lbfgs_minimize_batch_f32): `minimize` / `evaluate` take and return float32 CUDA tensors, `minimize_host`
+        float32 numpy arrays; More-Thuente, exact arithmetic, Rosenbrock / DiagQuadratic, n <= 256.  What that path does
+        not build is refused by the library with its reason (EngineError).  Only this class takes float32.
     """
 
     _entry = "mi355_lbfgs_minimize_batch"  # C-ABI entry point (subclasses: other solvers of the same shape)
 
     def __init__(self, m=10, stopping_progress=None, device=0, lanes_per_problem=0, elems_per_lane=0,
                  context=None, history_placement=0, linesearch="more_thuente", arithmetic="default",
-                 condition_hessian=0.0):
+                 condition_hessian=0.0, dtype=None):
         import torch
         self._torch = torch
+        self.dtype = torch.float64 if dtype is None else dtype
+        if self.dtype not in (torch.float64, torch.float32):
+            raise ValueError("dtype must be torch.float64 or torch.float32")
+        if self.dtype == torch.float32 and type(self) is not BatchedLbfgs:
+            raise ValueError("%s computes in float64 only: dtype=torch.float32 is built for BatchedLbfgs"
+                             % type(self).__name__)
+        self._f32 = self.dtype == torch.float32
+        self._np_dtype = np.float32 if self._f32 else np.float64
         self.m = int(m)
         self.stopping_progress = stopping_progress or capi.default_stop()
         self.lanes_per_problem = int(lanes_per_problem)
@@ -312,13 +331,13 @@ class BatchedLbfgs:
         current stream.
         """
         torch = self._torch
-        if x0.dtype != torch.float64 or x0.dim() != 2 or not x0.is_cuda:
-            raise ValueError("x0 must be a [B, n] float64 CUDA tensor")
+        if x0.dtype != self.dtype or x0.dim() != 2 or not x0.is_cuda:
+            raise ValueError("x0 must be a [B, n] %s CUDA tensor" % ("float32" if self._f32 else "float64"))
         self._on_device(x0, "x0")
         x0 = x0.contiguous()
         B, n = x0.shape
         x = torch.empty_like(x0)
-        f = torch.empty(B, dtype=torch.float64, device=x0.device)
+        f = torch.empty(B, dtype=self.dtype, device=x0.device)
         g = torch.empty_like(x0) if want_gradient else None
         prog = torch.empty(B * capi.PROGRESS_DTYPE.itemsize, dtype=torch.uint8, device=x0.device) \
             if want_progress else None
@@ -326,7 +345,7 @@ class BatchedLbfgs:
         if trace is not None:
             self._trace_keepalive = trace
             d.trace = trace.c_pointer()
-        capi.check(getattr(self.ctx._lib, self._entry)(
+        capi.check(getattr(self.ctx._lib, self._entry + ("_f32" if self._f32 else ""))(
             self.ctx.handle, C.byref(d), *self._config_args(), B, x0.data_ptr(), x.data_ptr(), f.data_ptr(),
             g.data_ptr() if g is not None else None, prog.data_ptr() if prog is not None else None,
             self._stream()))
@@ -334,7 +353,9 @@ class BatchedLbfgs:
 
     def minimize_host(self, objective, x0, per_problem=None):
         """Same through the host-pointer entry point (numpy in, numpy out, synchronous)."""
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        if self._f32 and np.asarray(x0).dtype != np.float32:
+            raise ValueError("x0 must be a [B, n] float32 array")
+        x0 = np.ascontiguousarray(x0, dtype=self._np_dtype)
         B, n = x0.shape
         pp_ptr, pp_stride = None, 0
         if per_problem is not None:
@@ -343,10 +364,10 @@ class BatchedLbfgs:
             pp_ptr, pp_stride = pp.ctypes.data, pp.shape[1]
         x = np.empty_like(x0)
         g = np.empty_like(x0)
-        f = np.empty(B)
+        f = np.empty(B, dtype=self._np_dtype)
         prog = np.zeros(B, dtype=capi.PROGRESS_DTYPE)
         d = self._desc(objective, n, pp_ptr, pp_stride)
-        capi.check(getattr(self.ctx._lib, self._entry + "_host")(
+        capi.check(getattr(self.ctx._lib, self._entry + ("_f32_host" if self._f32 else "_host"))(
             self.ctx.handle, C.byref(d), *self._config_args(), B, x0.ctypes.data, x.ctypes.data, f.ctypes.data,
             g.ctypes.data, prog.ctypes.data))
         return x, f, g, prog
@@ -355,12 +376,15 @@ class BatchedLbfgs:
         """One objective evaluation per row of x (device functor parity tests)."""
         torch = self._torch
         self._on_device(x, "x")
+        if self._f32 and x.dtype != torch.float32:
+            raise ValueError("x must be a [B, n] float32 CUDA tensor")
         x = x.contiguous()
         B, n = x.shape
-        f = torch.empty(B, dtype=torch.float64, device=x.device)
+        f = torch.empty(B, dtype=self.dtype, device=x.device)
         g = torch.empty_like(x)
         d = self._desc(objective, n, *self._pp_device(per_problem, B))
-        capi.check(self.ctx._lib.mi355_lbfgs_eval_batch(
+        entry = self.ctx._lib.mi355_lbfgs_eval_batch_f32 if self._f32 else self.ctx._lib.mi355_lbfgs_eval_batch
+        capi.check(entry(
             self.ctx.handle, C.byref(d), B, x.data_ptr(), f.data_ptr(), g.data_ptr(), self._stream()))
         return f, g
 
@@ -423,7 +447,8 @@ class BatchedBfgs(BatchedLbfgs):
     _entry = "mi355_bfgs_minimize_batch"
 
     def __init__(self, stopping_progress=None, device=0, context=None, linesearch="more_thuente",
-                 lanes_per_problem=0, elems_per_lane=0):
+                 lanes_per_problem=0, elems_per_lane=0, dtype=None):
+        _float64_only(self, dtype)
         # mapping 0 x 0: the library's choice (one column of H per lane at the padded widths 32 and 64); an explicit split
         # must cover exactly the padded width with a built shape (include/mi355_lbfgs.h) — same bits either way
         super().__init__(m=1, stopping_progress=stopping_progress, device=device, context=context,
@@ -457,7 +482,8 @@ class BatchedTrustRegionNewton(_ConfiguredSolver):
     _entry = "mi355_trust_region_newton_minimize_batch"
 
     def __init__(self, stopping_progress=None, device=0, context=None, lanes_per_problem=0, condition_hessian=0.0,
-                 **config):
+                 dtype=None, **config):
+        _float64_only(self, dtype)
         super().__init__(m=1, stopping_progress=stopping_progress, device=device, context=context,
                          arithmetic="exact", lanes_per_problem=lanes_per_problem, condition_hessian=condition_hessian)
         self.config = capi.default_trust_region_config(**config)
@@ -483,7 +509,8 @@ class BatchedNewtonDescent(BatchedTrustRegionNewton):
     _entry = "mi355_newton_descent_minimize_batch"
 
     def __init__(self, stopping_progress=None, device=0, context=None, lanes_per_problem=0, condition_hessian=0.0,
-                 **config):
+                 dtype=None, **config):
+        _float64_only(self, dtype)
         BatchedLbfgs.__init__(self, m=1, stopping_progress=stopping_progress, device=device, context=context,
                               arithmetic="exact", lanes_per_problem=lanes_per_problem,
                               condition_hessian=condition_hessian)
@@ -497,7 +524,9 @@ class BatchedGradientDescent(_ConfiguredSolver):
     _entry = "mi355_gradient_descent_minimize_batch"
     _config = None
 
-    def __init__(self, stopping_progress=None, device=0, context=None, lanes_per_problem=0, elems_per_lane=0):
+    def __init__(self, stopping_progress=None, device=0, context=None, lanes_per_problem=0, elems_per_lane=0,
+                 dtype=None):
+        _float64_only(self, dtype)
         super().__init__(m=1, stopping_progress=stopping_progress, device=device, context=context, arithmetic="exact",
                          lanes_per_problem=lanes_per_problem, elems_per_lane=elems_per_lane)
 
@@ -519,7 +548,8 @@ class BatchedConjugatedGradientDescent(BatchedGradientDescent):
     _entry = "mi355_conjugated_gradient_descent_minimize_batch"
 
     def __init__(self, stopping_progress=None, device=0, context=None, lanes_per_problem=0, elems_per_lane=0,
-                 armijo_c=None, armijo_rho=None, armijo_alpha_min=None):
+                 armijo_c=None, armijo_rho=None, armijo_alpha_min=None, dtype=None):
+        _float64_only(self, dtype)
         super().__init__(stopping_progress=stopping_progress, device=device, context=context,
                          lanes_per_problem=lanes_per_problem, elems_per_lane=elems_per_lane)
         given = dict(c=armijo_c, rho=armijo_rho, alpha_min=armijo_alpha_min)
@@ -541,7 +571,8 @@ class BatchedNelderMead(_ConfiguredSolver):
     reference's for this solver: the conservative preset with x_delta_violations = 5."""
     _entry = "mi355_nelder_mead_minimize_batch"
 
-    def __init__(self, stopping_progress=None, device=0, context=None, lanes_per_problem=0, **config):
+    def __init__(self, stopping_progress=None, device=0, context=None, lanes_per_problem=0, dtype=None, **config):
+        _float64_only(self, dtype)
         if stopping_progress is None:
             stopping_progress = capi.default_stop("conservative")   # nelder_mead.h:87-91
             stopping_progress.x_delta_violations = 5
@@ -569,7 +600,8 @@ class BatchedLbfgsb(BatchedLbfgs):
     gradient_norm is the projected-gradient tolerance."""
 
     def __init__(self, m=5, stopping_progress=None, device=0, context=None, linesearch="more_thuente",
-                 arithmetic="default"):
+                 arithmetic="default", dtype=None):
+        _float64_only(self, dtype)
         # arithmetic: "exact" = the reference-order kernels (lbfgsb_kernel.hpp, bit-identical to the oracle's butterfly
         # policy), "fma" = the relaxed-algebra kernels (lbfgsb_fast_kernel.hpp, bit-identical to their own CPU twin,
         # within 1e-6 of the reference), "default" = the library's choice (relaxed where it is built)

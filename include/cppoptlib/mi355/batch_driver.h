@@ -242,6 +242,17 @@ std::vector<double> PackStates(const std::vector<StateType>& states, int n) {
   return x0;
 }
 
+// states -> x0[B][n] in float (Lbfgs::SetNativeFloat: the states of a float function, unchanged)
+template <class StateType>
+std::vector<float> PackStatesAsFloat(const std::vector<StateType>& states, int n) {
+  std::vector<float> x0(states.size() * static_cast<size_t>(n));
+  for (size_t b = 0; b < states.size(); ++b) {
+    if (static_cast<int>(states[b].x.size()) != n) Fail("MinimizeBatch: mixed dimensions");
+    for (int i = 0; i < n; ++i) x0[b * n + i] = static_cast<float>(states[b].x[i]);
+  }
+  return x0;
+}
+
 // Per-problem data rows of the C-ABI (mi355_lbfgs_desc.per_problem_data) for function types that carry them
 // (HasPerProblemData: e.g. the ridge objective's right-hand side y).  ONE function object describes one problem, so
 // its row is replicated for the B start states; a vector of B function objects (the reference's README builds one

@@ -33,7 +33,8 @@ class Lbfgs : public Solver<FunctionType, cppoptlib::function::FunctionState<typ
                 "L-BFGS only supports first- or second-order differentiable functions");
   static_assert(std::is_floating_point<typename FunctionType::ScalarType>::value,
                 "ScalarType must be float or double (the MI355X engine computes in fp64 either way: a float function type is "
-                "widened at the boundary and its results are rounded back, see INTEGRATION.md)");
+                "widened at the boundary and its results are rounded back, see INTEGRATION.md; SetNativeFloat(true) opts a "
+                "float function into the native fp32 kernel)");
   static_assert(cppoptlib::mi355::kHasDeviceTwin<FunctionType>,
                 "FunctionType has no device twin (kDeviceObjective / DeviceParams, see "
                 "cppoptlib/mi355/objectives.h); the MI355X engine has no CPU fallback");
@@ -58,6 +59,25 @@ class Lbfgs : public Solver<FunctionType, cppoptlib::function::FunctionState<typ
   // mi355_arithmetic: MI355_ARITH_DEFAULT (the fused production kernels where they exist), MI355_ARITH_EXACT (the
   // bit-pinning build) or MI355_ARITH_FMA.
   void SetArithmetic(int arithmetic) { arithmetic_ = arithmetic; }
+  // Opt-in, off by default: a function whose ScalarType is float is solved by the native fp32 kernel
+  // (mi355_lbfgs_minimize_batch_f32_host: every operation in float, as the reference's Lbfgs<F, m> on a float function)
+  // instead of being widened to fp64.  Minimize and MinimizeBatch(function, states) take that path; First-mode
+  // functions, the More-Thuente search, no callback (the float kernel records no trace).  What the float kernel does
+  // not build (objectives other than Rosenbrock / DiagQuadratic, n > 256, MI355_ARITH_FMA) the library refuses.
+  void SetNativeFloat(bool on) {
+    if (on) {
+      if (!std::is_same<ScalarType, float>::value)
+        cppoptlib::mi355::Fail("Lbfgs::SetNativeFloat: the function's ScalarType is not float (a double function is solved in fp64)");
+      if (FunctionType::Differentiability == cppoptlib::function::DifferentiabilityMode::Second)
+        cppoptlib::mi355::Fail("Lbfgs::SetNativeFloat: the native fp32 kernel is built for First-mode functions");
+      if (kLineSearch != MI355_LS_MORE_THUENTE)
+        cppoptlib::mi355::Fail("Lbfgs::SetNativeFloat: the native fp32 kernel is built with the More-Thuente line search");
+      if (this->HasCallback())
+        cppoptlib::mi355::Fail("Lbfgs::SetNativeFloat: the native fp32 kernel records no trace, so a step callback cannot be replayed");
+    }
+    native_float_ = on;
+  }
+  bool NativeFloat() const { return native_float_; }
 
   // Lbfgs::Minimize of the reference (solver/solver.h:181-224): only `.x` of the incoming state is used, value and
   // gradient are evaluated at x0 (:189-192).  With a callback set the solve is traced on the device and the callback
@@ -65,6 +85,9 @@ class Lbfgs : public Solver<FunctionType, cppoptlib::function::FunctionState<typ
   std::tuple<StateType, ProgressType> Minimize(const FunctionType& function,
                                                const StateType& function_state) override {
     cppoptlib::mi355::RequireObjective(function, "Lbfgs");
+    if constexpr (std::is_same<ScalarType, float>::value) {
+      if (native_float_) return MinimizeBatchNativeFloat(function, std::vector<StateType>{function_state})[0];
+    }
     // (Second mode: every Update of the reference recomputes Progress::condition_hessian, progress.h:203-210, so the
     //  replayed records carry it too — the constant of this solve, or ||H(x)|| ||H(x)^-1|| of the host functor at the
     //  replayed point; the record of the start state is a fresh Progress, as there)
@@ -99,6 +122,9 @@ class Lbfgs : public Solver<FunctionType, cppoptlib::function::FunctionState<typ
                                                                  const std::vector<StateType>& states) {
     const int64_t B = static_cast<int64_t>(states.size());
     if (B == 0) return {};
+    if constexpr (std::is_same<ScalarType, float>::value) {
+      if (native_float_) return MinimizeBatchNativeFloat(function, states);
+    }
     const int n = static_cast<int>(states[0].x.size());
     const std::vector<double> x0 = cppoptlib::mi355::PackStates(states, n);
     std::vector<double> x(x0.size()), g(x0.size()), f(static_cast<size_t>(B));
@@ -239,6 +265,28 @@ class Lbfgs : public Solver<FunctionType, cppoptlib::function::FunctionState<typ
   }
 
  private:
+  // SetNativeFloat(true): the states packed as float, mi355_lbfgs_minimize_batch_f32_host, the float results widened
+  // (exactly) into the containers UnpackResults reads and rounded back to ScalarType = float (exactly) there.
+  std::vector<std::tuple<StateType, ProgressType>> MinimizeBatchNativeFloat(const FunctionType& function,
+                                                                            const std::vector<StateType>& states) {
+    if (this->HasCallback())
+      cppoptlib::mi355::Fail("Lbfgs::SetNativeFloat: the native fp32 kernel records no trace, so a step callback cannot be replayed");
+    const int64_t B = static_cast<int64_t>(states.size());
+    const int n = static_cast<int>(states[0].x.size());
+    const std::vector<float> x0 = cppoptlib::mi355::PackStatesAsFloat(states, n);
+    std::vector<float> x(x0.size()), g(x0.size()), f(static_cast<size_t>(B));
+    std::vector<mi355_lbfgs_progress> prog(static_cast<size_t>(B));
+    if (!ctx_) ctx_ = cppoptlib::mi355::Context::Default();
+    DescStorage st;
+    FillDesc(function, n, B, /*host_per_problem=*/true, &st);
+    cppoptlib::mi355::Check(mi355_lbfgs_minimize_batch_f32_host(ctx_->get(), &st.d, B, x0.data(), x.data(), f.data(),
+                                                                g.data(), prog.data()),
+                            "mi355_lbfgs_minimize_batch_f32_host");
+    return cppoptlib::mi355::UnpackResults<StateType, ProgressType, VectorType>(
+        n, B, std::vector<double>(x.begin(), x.end()), std::vector<double>(f.begin(), f.end()),
+        std::vector<double>(g.begin(), g.end()), prog);
+  }
+
   struct DescStorage {  // the desc and the host arrays it points into
     mi355_lbfgs_desc d{};
     std::vector<double> params, per_problem, hessian_diagonal;
@@ -323,6 +371,7 @@ class Lbfgs : public Solver<FunctionType, cppoptlib::function::FunctionState<typ
   }
 
   int arithmetic_ = MI355_ARITH_DEFAULT;
+  bool native_float_ = false;
   mutable double hessian_condition_ = 0;  // of the last Second-mode solve: reported in the returned Progress
   std::shared_ptr<cppoptlib::mi355::Context> ctx_;
 };

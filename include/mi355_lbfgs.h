@@ -326,6 +326,27 @@ int mi355_lbfgs_minimize_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc
                                     const double* x0, double* x_out, double* f_out, double* g_out,
                                     mi355_lbfgs_progress* progress_out);
 
+/* Lbfgs<F, m, MoreThuente> with FunctionType::ScalarType = float, computed in float from the kernel up (opt-in: the
+ * entry points above widen a float function to fp64, as before).  x0, x_out, f_out, g_out are float arrays (DEVICE
+ * pointers; g_out and progress_out may be NULL); `desc` is the same struct: DiagQuadratic's objective_params are each
+ * converted once with (float), and so is every threshold of desc->stop.  The progress record's three doubles are the
+ * float values widened.  A NaN among x, f, g and those three doubles is written as the canonical quiet NaN.
+ * Built for Rosenbrock and DiagQuadratic, n <= 256, m <= MI355_LBFGS_MAX_M, exact arithmetic, both halves of the history
+ * in LDS; lanes_per_problem 8, 16, 32, 64 at one coordinate per lane or 64 at two / four (0 / 0: the padded width up to
+ * 64 lanes, then 64 x 2 and 64 x 4).  MI355_ERR_UNSUPPORTED with the reason, before anything is launched, for: other
+ * objectives, Hager-Zhang, MI355_ARITH_FMA, MI355_HISTORY_Y_IN_REGISTERS, hessian_from_functor / hessian_diagonal /
+ * hessian_condition_stop > 0, a trace, per_problem_data, n > 256, another mapping. */
+int mi355_lbfgs_minimize_batch_f32(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const float* x0,
+                                   float* x_out, float* f_out, float* g_out, mi355_lbfgs_progress* progress_out,
+                                   void* stream);
+/* Same with HOST arrays, synchronous, through the context's pinned staging slot; batches beyond a slot are solved in
+ * chunks, one after the other. */
+int mi355_lbfgs_minimize_batch_f32_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const float* x0,
+                                        float* x_out, float* f_out, float* g_out, mi355_lbfgs_progress* progress_out);
+/* One float evaluation of the objective per row of x (DEVICE pointers; g_out may be NULL). */
+int mi355_lbfgs_eval_batch_f32(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const float* x,
+                               float* f_out, float* g_out, void* stream);
+
 /* Batched Lbfgsb::Minimize — box-constrained L-BFGS-B (solver/lbfgsb.h:141-292, Cauchy point
  * :318-430, subspace minimisation :459-515).  `lower` / `upper`: n doubles each, shared by the
  * batch (SetBounds, lbfgsb.h:89-93), or both NULL for the reference's default unbounded box
