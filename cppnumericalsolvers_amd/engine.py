@@ -417,6 +417,50 @@ class BatchedLbfgs:
             self._stream()))
         return x0
 
+    def minimize_callable(self, fn, x0, check_every=1, max_rounds=None):
+        """Batched Solver::Minimize of an objective the CALLER evaluates (ask/tell, `LbfgsAskTell`): `fn(X)` takes the
+        [B, n] float64 CUDA tensor of the points to evaluate and returns (f [B], g [B, n]) — or f alone, and the gradient
+        is then torch.autograd.grad(f.sum(), X) on a leaf that requires grad (the problems are independent, so the
+        sum's gradient is the per-problem gradient).  X is the solver's own buffer: read it, do not keep or write it.
+        check_every=k reads the active count back every k rounds (a round on a finished batch changes nothing);
+        max_rounds: RuntimeError when the batch is still active after that many rounds.
+        Returns (x, f, g, progress) like `minimize`."""
+        if int(check_every) < 1:
+            raise ValueError("check_every must be >= 1")
+        torch = self._torch
+        value_only = [None]   # which of the two forms fn has: the first round tells
+
+        def evaluate(X):
+            if value_only[0] is None:
+                with torch.no_grad():
+                    out = fn(X)
+                value_only[0] = not isinstance(out, (tuple, list))
+                if not value_only[0]:
+                    return out
+            if not value_only[0]:
+                return fn(X)
+            leaf = X.detach().requires_grad_(True)
+            f = fn(leaf)
+            (g,) = torch.autograd.grad(f.sum(), leaf)
+            return f.detach(), g
+
+        with LbfgsAskTell(self, x0) as at:
+            rounds = 0
+            while at.B > 0:
+                f, g = evaluate(at.x)
+                rounds += 1
+                if rounds % int(check_every) == 0:
+                    if at.tell(f, g) == 0:
+                        break
+                else:
+                    at.tell(f, g, wait=False)
+                if max_rounds is not None and rounds >= int(max_rounds):
+                    if at.active == 0:
+                        break
+                    raise RuntimeError("minimize_callable: %d problems still active after max_rounds = %d rounds"
+                                       % (at.active, int(max_rounds)))
+            return at.results()
+
     def last_kernel_ms(self):
         ms = C.c_float()
         capi.check(self.ctx._lib.mi355_lbfgs_last_kernel_ms(self.ctx.handle, C.byref(ms)))
@@ -439,6 +483,121 @@ class BatchedLbfgs:
         capi.check(self.ctx._lib.mi355_lbfgs_last_kernel_variant(self.ctx.handle, C.byref(k)))
         out["kernel"] = {0: "general", 1: "lean"}[k.value]
         return out
+
+
+class _DeviceArray:
+    """A device buffer the library owns, described through __cuda_array_interface__ so that torch.as_tensor makes a
+    tensor VIEW of it (no copy); `owner` keeps the allocation alive for as long as the view exists."""
+
+    def __init__(self, ptr, shape, typestr, owner):
+        self.owner = owner
+        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr=typestr, data=(int(ptr), False), version=2,
+                                             strides=None)
+
+
+class LbfgsAskTell:
+    """One ask/tell solve (mi355_lbfgs_ask_tell_*): `Lbfgs<F, m, MoreThuente>::Minimize` of B problems whose objective
+    the caller evaluates.  The solver state of all problems lives on the device; every `tell` runs one kernel that takes
+    each problem to its next evaluation.
+
+        at = amd.LbfgsAskTell(solver, x0)          # solver: a float64 BatchedLbfgs (m, stopping_progress, mapping)
+        while at.tell(*my_value_and_gradient(at.x)) > 0:
+            pass
+        x, f, g, progress = at.results()
+
+    .x: the [B, n] float64 tensor VIEW of the evaluation buffer (no copy; valid until close()); rows of finished
+    problems hold their returned x, and what is handed back for them is never read.  A solver configured with what the
+    path does not build (Hager-Zhang, arithmetic="fma", y history in registers, condition_hessian) raises the
+    library's message (EngineError).  Everything runs on the current stream of the solver's device."""
+
+    def __init__(self, solver, x0):
+        if type(solver) is not BatchedLbfgs:
+            raise TypeError("LbfgsAskTell takes a BatchedLbfgs (the other solvers have no ask/tell form)")
+        if solver._f32:
+            raise ValueError("LbfgsAskTell computes in float64: the solver was built with dtype=torch.float32")
+        torch = solver._torch
+        if x0.dtype != torch.float64 or x0.dim() != 2 or not x0.is_cuda:
+            raise ValueError("x0 must be a [B, n] float64 CUDA tensor")
+        solver._on_device(x0, "x0")
+        x0 = x0.contiguous()
+        self._h = None
+        self.solver = solver
+        self.B, self.n = (int(v) for v in x0.shape)
+        self._lib = solver.ctx._lib
+        d = solver._desc(Objective(capi.OBJ_ROSENBROCK, np.zeros(0), "caller"), self.n)
+        d.hessian_condition_stop = solver.condition_hessian
+        h = C.c_void_p()
+        capi.check(self._lib.mi355_lbfgs_ask_tell_create(solver.ctx.handle, C.byref(d), self.B, x0.data_ptr(),
+                                                         solver._stream(), C.byref(h)))
+        self._h = h
+        p = C.c_void_p()
+        capi.check(self._lib.mi355_lbfgs_ask_tell_x(self._h, C.byref(p)))
+        self.x = torch.as_tensor(_DeviceArray(p.value, (self.B, self.n), "<f8", self), device=solver.device) \
+            if self.B > 0 else torch.empty(0, self.n, dtype=torch.float64, device=solver.device)
+        capi.check(self._lib.mi355_lbfgs_ask_tell_active(self._h, C.byref(p)))
+        self._active_dev = torch.as_tensor(_DeviceArray(p.value, (1,), "<i8", self), device=solver.device)
+
+    def _rows(self, t, shape, what):
+        torch = self.solver._torch
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_cuda:
+            raise ValueError("%s must be a %s float64 CUDA tensor" % (what, list(shape)))
+        self.solver._on_device(t, what)
+        return t.detach().contiguous()
+
+    def tell(self, f, g, wait=True):
+        """Hands the values f [B] and gradients g [B, n] at the rows of .x to the solver and advances every problem to
+        its next evaluation.  wait=True: returns the number of problems still active (waits for the stream);
+        wait=False: returns None and nothing waits (`.active` reads the count later)."""
+        if self._h is None:
+            raise RuntimeError("this LbfgsAskTell is closed")
+        f = self._rows(f, (self.B,), "f")
+        g = self._rows(g, (self.B, self.n), "g")
+        count = C.c_int64(-1)
+        capi.check(self._lib.mi355_lbfgs_ask_tell_step(self._h, f.data_ptr(), g.data_ptr(),
+                                                       C.byref(count) if wait else None, self.solver._stream()))
+        return int(count.value) if wait else None
+
+    @property
+    def active(self):
+        """The number of problems that have not finished (reads the device counter: waits for the stream)."""
+        if self._h is None:
+            raise RuntimeError("this LbfgsAskTell is closed")
+        return int(self._active_dev.item())
+
+    def results(self):
+        """(x, f, g, progress) like BatchedLbfgs.minimize: the current iterate of every problem (the returned state of
+        a finished one); at any time between two tells."""
+        if self._h is None:
+            raise RuntimeError("this LbfgsAskTell is closed")
+        torch = self.solver._torch
+        dev = self.solver.device
+        x = torch.empty(self.B, self.n, dtype=torch.float64, device=dev)
+        g = torch.empty(self.B, self.n, dtype=torch.float64, device=dev)
+        f = torch.empty(self.B, dtype=torch.float64, device=dev)
+        prog = torch.empty(self.B * capi.PROGRESS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        capi.check(self._lib.mi355_lbfgs_ask_tell_results(self._h, x.data_ptr(), f.data_ptr(), g.data_ptr(),
+                                                          prog.data_ptr(), self.solver._stream()))
+        return x, f, g, prog
+
+    def close(self):
+        """Frees the device state (waits for the device); .x must not be used afterwards."""
+        if getattr(self, "_h", None) is not None:
+            h, self._h = self._h, None
+            self.x = self._active_dev = None
+            capi.check(self._lib.mi355_lbfgs_ask_tell_destroy(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class BatchedBfgs(BatchedLbfgs):

@@ -662,6 +662,45 @@ int mi355_check_derivatives_batch_host(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_d
                                        double* f_out, double* grad_out, double* grad_fd_out, double* hess_out,
                                        double* hess_fd_out, mi355_derivative_report* report_out);
 
+/* ---- ask/tell (reverse communication) L-BFGS: objectives the CALLER evaluates ------------------------------------
+ * Lbfgs<F, m, MoreThuente>::Minimize for B problems whose objective is not a device functor of this library: the solver
+ * state of every problem (iterate, gradient, direction, the (s, y) rings, the scalars of the More-Thuente search and of
+ * Progress) lives in device memory owned by a handle; one call of _step runs ONE kernel that advances every problem up
+ * to its next objective evaluation and writes the point to evaluate into the evaluation buffer x_eval [B][n]; the
+ * caller evaluates all B rows however it likes (torch ops, autograd, its own kernels, hipBLAS) and hands f [B] and
+ * g [B][n] back.  Each problem keeps its own line search, history and stopping tests; only the evaluation is outside.
+ * Protocol: after _create x_eval holds x0; evaluate all rows, call _step, repeat until the active count is 0.  Rows of
+ * problems that have finished hold the returned x, their f / g rows are never read (any value, NaN included, is fine),
+ * and further _step calls on a finished batch change nothing.  A problem whose line search is refused at once
+ * (g.s >= 0, more_thuente.h:152-156) asks for no evaluation in that round: its f / g rows are not read either.
+ * A callback that evaluates with mi355_lbfgs_eval_batch reproduces mi355_lbfgs_minimize_batch under MI355_ARITH_EXACT
+ * bit for bit (x, f, g and every field of the progress record).
+ * Of desc: n, m, stop, lanes_per_problem and elems_per_lane are read (mappings: 8, 16, 32, 64 lanes at one coordinate
+ * per lane, 64 lanes at two or four; 0 / 0: the padded width up to 64 lanes, then 64 x 2 and 64 x 4); objective and the
+ * parameter fields are ignored.  MI355_ERR_UNSUPPORTED with the reason, before anything is allocated or launched, for:
+ * Hager-Zhang, MI355_ARITH_FMA, MI355_HISTORY_Y_IN_REGISTERS, hessian_from_functor, hessian_diagonal,
+ * hessian_condition_stop > 0, a trace, per_problem_data, n > 256, a mapping that is not built.  Device memory per
+ * problem: (4 + 2 m) P doubles (P = lanes x coordinates per lane) and 536 bytes of scalars.
+ * The progress record means what it means for mi355_lbfgs_minimize_batch; nfev counts the evaluations consumed. */
+typedef struct mi355_lbfgs_ask_tell mi355_lbfgs_ask_tell;
+/* x0: DEVICE [B][n], copied on `stream`; the handle keeps ctx (destroy the handle first). */
+int mi355_lbfgs_ask_tell_create(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const double* x0,
+                                void* stream, mi355_lbfgs_ask_tell** out);
+/* The evaluation buffer: DEVICE [B][n], owned by the handle, the same pointer for the handle's lifetime. */
+int mi355_lbfgs_ask_tell_x(mi355_lbfgs_ask_tell* handle, const double** x_eval);
+/* f: DEVICE [B], g: DEVICE [B][n], the caller's evaluation of the rows of x_eval.  active_host != NULL: waits for
+ * `stream` and writes the number of problems that are not finished; NULL: nothing waits (the count is behind
+ * mi355_lbfgs_ask_tell_active once the stream has run the call). */
+int mi355_lbfgs_ask_tell_step(mi355_lbfgs_ask_tell* handle, const double* f, const double* g, int64_t* active_host,
+                              void* stream);
+/* DEVICE pointer to that count (B after _create). */
+int mi355_lbfgs_ask_tell_active(mi355_lbfgs_ask_tell* handle, const int64_t** active_dev);
+/* The current iterate of every problem with its value, gradient and progress record (the returned state of a finished
+ * problem); at any time between steps.  DEVICE pointers, any may be NULL; asynchronous on `stream`. */
+int mi355_lbfgs_ask_tell_results(mi355_lbfgs_ask_tell* handle, double* x_out, double* f_out, double* g_out,
+                                 mi355_lbfgs_progress* progress_out, void* stream);
+int mi355_lbfgs_ask_tell_destroy(mi355_lbfgs_ask_tell* handle);
+
 /* Duration in ms of the most recent solve kernel on this context, measured with
  * HIP events recorded on the launch stream; blocks until that kernel finished. */
 int mi355_lbfgs_last_kernel_ms(mi355_lbfgs_ctx* ctx, float* ms);
