@@ -444,7 +444,7 @@ class BatchedLbfgs:
             (g,) = torch.autograd.grad(f.sum(), leaf)
             return f.detach(), g
 
-        with LbfgsAskTell(self, x0) as at:
+        with self._ask_tell(x0) as at:
             rounds = 0
             while at.B > 0:
                 f, g = evaluate(at.x)
@@ -460,6 +460,10 @@ class BatchedLbfgs:
                     raise RuntimeError("minimize_callable: %d problems still active after max_rounds = %d rounds"
                                        % (at.active, int(max_rounds)))
             return at.results()
+
+    def _ask_tell(self, x0):
+        """The ask/tell handle of this solver class (minimize_callable's)."""
+        return LbfgsAskTell(self, x0)
 
     def last_kernel_ms(self):
         ms = C.c_float()
@@ -510,31 +514,42 @@ class LbfgsAskTell:
     path does not build (Hager-Zhang, arithmetic="fma", y history in registers, condition_hessian) raises the
     library's message (EngineError).  Everything runs on the current stream of the solver's device."""
 
-    def __init__(self, solver, x0):
+    _prefix = "mi355_lbfgs_ask_tell_"
+
+    def _call(self, name, *args):
+        capi.check(getattr(self._lib, self._prefix + name)(*args))
+
+    def _check_solver(self, solver):
         if type(solver) is not BatchedLbfgs:
-            raise TypeError("LbfgsAskTell takes a BatchedLbfgs (the other solvers have no ask/tell form)")
+            raise TypeError("LbfgsAskTell takes a BatchedLbfgs (BatchedLbfgsb has LbfgsbAskTell; the other solvers have "
+                            "no ask/tell form)")
         if solver._f32:
             raise ValueError("LbfgsAskTell computes in float64: the solver was built with dtype=torch.float32")
+
+    def _create(self, solver, d, x0, h):
+        self._call("create", solver.ctx.handle, C.byref(d), self.B, x0.data_ptr(), solver._stream(), C.byref(h))
+
+    def __init__(self, solver, x0):
+        self._h = None
+        self._check_solver(solver)
         torch = solver._torch
         if x0.dtype != torch.float64 or x0.dim() != 2 or not x0.is_cuda:
             raise ValueError("x0 must be a [B, n] float64 CUDA tensor")
         solver._on_device(x0, "x0")
         x0 = x0.contiguous()
-        self._h = None
         self.solver = solver
         self.B, self.n = (int(v) for v in x0.shape)
         self._lib = solver.ctx._lib
         d = solver._desc(Objective(capi.OBJ_ROSENBROCK, np.zeros(0), "caller"), self.n)
         d.hessian_condition_stop = solver.condition_hessian
         h = C.c_void_p()
-        capi.check(self._lib.mi355_lbfgs_ask_tell_create(solver.ctx.handle, C.byref(d), self.B, x0.data_ptr(),
-                                                         solver._stream(), C.byref(h)))
+        self._create(solver, d, x0, h)
         self._h = h
         p = C.c_void_p()
-        capi.check(self._lib.mi355_lbfgs_ask_tell_x(self._h, C.byref(p)))
+        self._call("x", self._h, C.byref(p))
         self.x = torch.as_tensor(_DeviceArray(p.value, (self.B, self.n), "<f8", self), device=solver.device) \
             if self.B > 0 else torch.empty(0, self.n, dtype=torch.float64, device=solver.device)
-        capi.check(self._lib.mi355_lbfgs_ask_tell_active(self._h, C.byref(p)))
+        self._call("active", self._h, C.byref(p))
         self._active_dev = torch.as_tensor(_DeviceArray(p.value, (1,), "<i8", self), device=solver.device)
 
     def _rows(self, t, shape, what):
@@ -549,34 +564,32 @@ class LbfgsAskTell:
         its next evaluation.  wait=True: returns the number of problems still active (waits for the stream);
         wait=False: returns None and nothing waits (`.active` reads the count later)."""
         if self._h is None:
-            raise RuntimeError("this LbfgsAskTell is closed")
+            raise RuntimeError("this %s is closed" % type(self).__name__)
         f = self._rows(f, (self.B,), "f")
         g = self._rows(g, (self.B, self.n), "g")
         count = C.c_int64(-1)
-        capi.check(self._lib.mi355_lbfgs_ask_tell_step(self._h, f.data_ptr(), g.data_ptr(),
-                                                       C.byref(count) if wait else None, self.solver._stream()))
+        self._call("step", self._h, f.data_ptr(), g.data_ptr(), C.byref(count) if wait else None, self.solver._stream())
         return int(count.value) if wait else None
 
     @property
     def active(self):
         """The number of problems that have not finished (reads the device counter: waits for the stream)."""
         if self._h is None:
-            raise RuntimeError("this LbfgsAskTell is closed")
+            raise RuntimeError("this %s is closed" % type(self).__name__)
         return int(self._active_dev.item())
 
     def results(self):
         """(x, f, g, progress) like BatchedLbfgs.minimize: the current iterate of every problem (the returned state of
         a finished one); at any time between two tells."""
         if self._h is None:
-            raise RuntimeError("this LbfgsAskTell is closed")
+            raise RuntimeError("this %s is closed" % type(self).__name__)
         torch = self.solver._torch
         dev = self.solver.device
         x = torch.empty(self.B, self.n, dtype=torch.float64, device=dev)
         g = torch.empty(self.B, self.n, dtype=torch.float64, device=dev)
         f = torch.empty(self.B, dtype=torch.float64, device=dev)
         prog = torch.empty(self.B * capi.PROGRESS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        capi.check(self._lib.mi355_lbfgs_ask_tell_results(self._h, x.data_ptr(), f.data_ptr(), g.data_ptr(),
-                                                          prog.data_ptr(), self.solver._stream()))
+        self._call("results", self._h, x.data_ptr(), f.data_ptr(), g.data_ptr(), prog.data_ptr(), self.solver._stream())
         return x, f, g, prog
 
     def close(self):
@@ -584,7 +597,7 @@ class LbfgsAskTell:
         if getattr(self, "_h", None) is not None:
             h, self._h = self._h, None
             self.x = self._active_dev = None
-            capi.check(self._lib.mi355_lbfgs_ask_tell_destroy(h))
+            self._call("destroy", h)
 
     def __enter__(self):
         return self
@@ -756,7 +769,8 @@ class BatchedLbfgsb(BatchedLbfgs):
     reference solvers with B SetBounds calls solve; see mi355_lbfgsb_minimize_batch_boxes for the built range — at
     32 < n <= 64 arithmetic="default" is the reference-order kernel there).  stopping_progress defaults to what a
     default-constructed reference Lbfgsb uses (f_delta = 2.22e-9 relative on top of the default preset); its
-    gradient_norm is the projected-gradient tolerance."""
+    gradient_norm is the projected-gradient tolerance.  `minimize_callable(fn, x0)` minimises an objective the caller
+    evaluates (torch ops, autograd) under the box in force — `LbfgsbAskTell`; n <= 64, m <= 8, reference-order arithmetic."""
 
     def __init__(self, m=5, stopping_progress=None, device=0, context=None, linesearch="more_thuente",
                  arithmetic="default", dtype=None):
@@ -864,6 +878,52 @@ class BatchedLbfgsb(BatchedLbfgs):
             hi.ctypes.data if hi is not None else None, B, x0.ctypes.data, x.ctypes.data, f.ctypes.data,
             g.ctypes.data, prog.ctypes.data))
         return x, f, g, prog
+
+    def _ask_tell(self, x0):
+        return LbfgsbAskTell(self, x0)
+
+
+class LbfgsbAskTell(LbfgsAskTell):
+    """One ask/tell solve of `Lbfgsb<F, m, MoreThuente>::Minimize` (mi355_lbfgsb_ask_tell_*): B box-constrained problems
+    whose objective the caller evaluates — the batched counterpart of scipy's L-BFGS-B with a loss written in torch.
+
+        box = amd.BatchedLbfgsb(m=5); box.SetBounds(lower, upper)        # or SetBoundsPerProblem, or no box at all
+        at = amd.LbfgsbAskTell(box, x0)
+        while at.tell(*my_value_and_gradient(at.x)) > 0:
+            pass
+        x, f, g, progress = at.results()
+
+    The protocol, `.x`, `tell`, `active`, `results` and `close` are LbfgsAskTell's.  The box in force on the solver is
+    copied at creation.  `.asks`: how many problems asked for each kind of evaluation so far.  Built for n <= 64, m <= 8,
+    the More-Thuente search and the reference-order arithmetic (arithmetic="default" is that here; "fma" is refused)."""
+    _prefix = "mi355_lbfgsb_ask_tell_"
+    ASK_KINDS = ("clip_start", "trial", "cauchy", "clip_next", "first")
+
+    def _check_solver(self, solver):
+        if type(solver) is not BatchedLbfgsb:
+            raise TypeError("LbfgsbAskTell takes a BatchedLbfgsb (BatchedLbfgs has LbfgsAskTell)")
+
+    def _create(self, solver, d, x0, h):
+        rows = solver._own_boxes(self.B, self.n)
+        if rows is not None:
+            lower, upper, stride = rows[0], rows[1], self.n
+        else:
+            lower, upper, stride = solver._lower, solver._upper, 0
+            if lower is not None and lower.numel() != self.n:
+                raise ValueError("bounds have %d entries, problems have %d" % (lower.numel(), self.n))
+        self._call("create", solver.ctx.handle, C.byref(d), lower.data_ptr() if lower is not None else None,
+                   upper.data_ptr() if upper is not None else None, stride, self.B, x0.data_ptr(), solver._stream(),
+                   C.byref(h))
+
+    @property
+    def asks(self):
+        """{kind: count} over "clip_start", "trial", "cauchy", "clip_next", "first" (waits for the stream); once every
+        problem has finished the counts add up to the sum of nfev."""
+        if self._h is None:
+            raise RuntimeError("this %s is closed" % type(self).__name__)
+        counts = (C.c_int64 * len(self.ASK_KINDS))()
+        self._call("asks", self._h, counts, self.solver._stream())
+        return dict(zip(self.ASK_KINDS, (int(v) for v in counts)))
 
 
 class DeviceGroup:

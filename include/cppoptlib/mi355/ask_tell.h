@@ -5,7 +5,9 @@
 //   LbfgsAskTell        RAII handle of one batched solve: Ask() is the device pointer of the points to evaluate
 //                       ([B][n], the same pointer for the handle's lifetime), Tell(f_dev, g_dev) hands the values and
 //                       gradients back and returns the number of problems still active, Results(...) copies the states.
-//   MinimizeBatchWith   the loop around it: evaluator(x_dev, f_dev, g_dev, B, n) is the user's — its own kernels,
+//   LbfgsbAskTell       the same for Lbfgsb<F, m, MoreThuente>: no box, one shared box, or one box per problem
+//                       (mi355_lbfgsb_ask_tell_*), plus Asks(), the count of every kind of evaluation asked for
+//   MinimizeBatchWith   the loop around either: evaluator(x_dev, f_dev, g_dev, B, n) is the user's — its own kernels,
 //                       hipBLAS, anything that leaves f [B] and g [B][n] in device memory, ordered on `stream`.
 //
 // Plain C++17: no HIP header is needed here; the device arrays are the caller's.  Failures surface through Fail()
@@ -97,12 +99,107 @@ class LbfgsAskTell {
   int n_ = 0;
 };
 
+// ---- Lbfgsb<F, m, MoreThuente> in the same form (mi355_lbfgsb_ask_tell_*): simple bounds on the parameters -------------
+// The fields of mi355_lbfgs_desc the path reads, with the reference's Lbfgsb defaults (m = 5, the default stopping
+// progress with f_delta = 2.22e-9 relative, lbfgsb.h:84-87); the mapping is the library's.
+inline mi355_lbfgs_desc LbfgsbAskTellDesc(int n, int m = 5, const mi355_lbfgs_stop* stop = nullptr) {
+  mi355_lbfgs_desc d = {};
+  d.objective = MI355_OBJ_ROSENBROCK;  // not read: the caller evaluates
+  d.linesearch = MI355_LS_MORE_THUENTE;
+  d.n = n;
+  d.m = m;
+  d.arithmetic = MI355_ARITH_EXACT;
+  if (stop != nullptr) {
+    d.stop = *stop;
+  } else {
+    Check(mi355_lbfgs_default_stop(2, &d.stop), "mi355_lbfgs_default_stop");
+  }
+  return d;
+}
+
+// How many problems asked for each kind of evaluation so far (LbfgsbAskTell::Asks); finished batch: the sum is the sum
+// of nfev.
+struct LbfgsbAsks {
+  int64_t clip_start = 0, trial = 0, cauchy = 0, clip_next = 0, first = 0;
+};
+
+class LbfgsbAskTell {
+ public:
+  // No box: the reference's default unbounded one.  x0_dev: DEVICE [B][n]; stream as for LbfgsAskTell.
+  LbfgsbAskTell(std::shared_ptr<Context> context, const mi355_lbfgs_desc& desc, int64_t B, const double* x0_dev,
+                void* stream = nullptr)
+      : LbfgsbAskTell(std::move(context), desc, nullptr, nullptr, 0, B, x0_dev, stream) {}
+  // One box shared by the batch: lower_dev / upper_dev are DEVICE arrays of n doubles.
+  LbfgsbAskTell(std::shared_ptr<Context> context, const mi355_lbfgs_desc& desc, const double* lower_dev,
+                const double* upper_dev, int64_t B, const double* x0_dev, void* stream = nullptr)
+      : LbfgsbAskTell(std::move(context), desc, lower_dev, upper_dev, 0, B, x0_dev, stream) {}
+  // One box per problem: DEVICE rows of box_stride >= n doubles.  The handle copies the box: the caller's may go.
+  LbfgsbAskTell(std::shared_ptr<Context> context, const mi355_lbfgs_desc& desc, const double* lower_dev,
+                const double* upper_dev, int64_t box_stride, int64_t B, const double* x0_dev, void* stream = nullptr)
+      : context_(std::move(context)), stream_(stream), B_(B), n_(desc.n) {
+    if (!context_) Fail("LbfgsbAskTell: null context");
+    Check(mi355_lbfgsb_ask_tell_create(context_->get(), &desc, lower_dev, upper_dev, box_stride, B, x0_dev, stream_, &handle_),
+          "mi355_lbfgsb_ask_tell_create");
+    Check(mi355_lbfgsb_ask_tell_x(handle_, &x_), "mi355_lbfgsb_ask_tell_x");
+  }
+  ~LbfgsbAskTell() { (void)mi355_lbfgsb_ask_tell_destroy(handle_); }
+  LbfgsbAskTell(const LbfgsbAskTell&) = delete;
+  LbfgsbAskTell& operator=(const LbfgsbAskTell&) = delete;
+  LbfgsbAskTell(LbfgsbAskTell&& other) noexcept
+      : context_(std::move(other.context_)), handle_(other.handle_), x_(other.x_), stream_(other.stream_), B_(other.B_),
+        n_(other.n_) {
+    other.handle_ = nullptr;
+  }
+  LbfgsbAskTell& operator=(LbfgsbAskTell&&) = delete;
+
+  const double* Ask() const { return x_; }
+  int64_t Tell(const double* f_dev, const double* g_dev) {
+    int64_t active = 0;
+    Check(mi355_lbfgsb_ask_tell_step(handle_, f_dev, g_dev, &active, stream_), "mi355_lbfgsb_ask_tell_step");
+    return active;
+  }
+  void TellAsync(const double* f_dev, const double* g_dev) {
+    Check(mi355_lbfgsb_ask_tell_step(handle_, f_dev, g_dev, nullptr, stream_), "mi355_lbfgsb_ask_tell_step");
+  }
+  const int64_t* ActiveDevice() const {
+    const int64_t* p = nullptr;
+    Check(mi355_lbfgsb_ask_tell_active(handle_, &p), "mi355_lbfgsb_ask_tell_active");
+    return p;
+  }
+  void Results(double* x_dev, double* f_dev, double* g_dev, mi355_lbfgs_progress* progress_dev) const {
+    Check(mi355_lbfgsb_ask_tell_results(handle_, x_dev, f_dev, g_dev, progress_dev, stream_), "mi355_lbfgsb_ask_tell_results");
+  }
+  // waits for the stream
+  LbfgsbAsks Asks() const {
+    int64_t c[5] = {0, 0, 0, 0, 0};
+    Check(mi355_lbfgsb_ask_tell_asks(handle_, c, stream_), "mi355_lbfgsb_ask_tell_asks");
+    LbfgsbAsks a;
+    a.clip_start = c[0];
+    a.trial = c[1];
+    a.cauchy = c[2];
+    a.clip_next = c[3];
+    a.first = c[4];
+    return a;
+  }
+  int64_t batch() const { return B_; }
+  int dimension() const { return n_; }
+  void* stream() const { return stream_; }
+
+ private:
+  std::shared_ptr<Context> context_;
+  mi355_lbfgsb_ask_tell* handle_ = nullptr;
+  const double* x_ = nullptr;
+  void* stream_ = nullptr;
+  int64_t B_ = 0;
+  int n_ = 0;
+};
+
 // The loop: evaluate, tell, until no problem is active.  f_dev [B] and g_dev [B][n] are the caller's work arrays; the
 // evaluator must order its work on solve.stream().  max_rounds < 0: no limit; otherwise Fail() when the batch is still
 // active after that many rounds.  Returns the number of rounds (= evaluations of the batch).
-template <class Evaluator>
-int64_t MinimizeBatchWith(Evaluator&& evaluator, LbfgsAskTell& solve, double* f_dev, double* g_dev,
-                          int64_t max_rounds = -1) {
+// Handle: LbfgsAskTell or LbfgsbAskTell.
+template <class Evaluator, class Handle>
+int64_t MinimizeBatchWith(Evaluator&& evaluator, Handle& solve, double* f_dev, double* g_dev, int64_t max_rounds = -1) {
   int64_t rounds = 0;
   if (solve.batch() == 0) return rounds;
   while (true) {

@@ -701,6 +701,38 @@ int mi355_lbfgs_ask_tell_results(mi355_lbfgs_ask_tell* handle, double* x_out, do
                                  mi355_lbfgs_progress* progress_out, void* stream);
 int mi355_lbfgs_ask_tell_destroy(mi355_lbfgs_ask_tell* handle);
 
+/* ---- ask/tell (reverse communication) L-BFGS-B: bounds for objectives the CALLER evaluates -------------------------
+ * Lbfgsb<F, m, MoreThuente>::Minimize (solver/lbfgsb.h:141-292) in the same protocol as mi355_lbfgs_ask_tell_*: the
+ * batched counterpart of "B small problems, my loss in torch, simple bounds on the parameters".  The iteration is cut at
+ * its FIVE evaluations — the start point, clip(x) of an infeasible iterate, a trial point of the More-Thuente search, the
+ * Cauchy point when no variable is free, clip(next.x) when the step left the box —; a problem whose search is refused at
+ * once asks for nothing in that round.  A callback that evaluates with mi355_lbfgs_eval_batch reproduces
+ * mi355_lbfgsb_minimize_batch / _boxes under MI355_ARITH_EXACT bit for bit (x, f, g, every field of the progress record).
+ * The box: lower == upper == NULL is the reference's default unbounded box; box_stride == 0 one shared box of n doubles;
+ * otherwise one row of box_stride >= n doubles per problem.  DEVICE pointers; the handle copies the box at creation (the
+ * caller may free or change theirs) and refuses a NaN bound (MI355_ERR_INVALID_ARGUMENT; _create then waits for `stream`).
+ * Of desc: n, m and stop are read; objective and the parameter fields are ignored; MI355_ARITH_DEFAULT is the
+ * reference-order arithmetic here.  MI355_ERR_UNSUPPORTED with a message that starts "Lbfgsb ask/tell" and names the
+ * reason, before anything is allocated or launched, for: Hager-Zhang, MI355_ARITH_FMA, m > 8, n > 64, a trace,
+ * per_problem_data, hessian_from_functor, hessian_diagonal, hessian_condition_stop > 0, a non-zero lanes_per_problem /
+ * elems_per_lane / history_placement.  Device memory per problem: (4 + 2 m) P + 2 M^2 doubles (P = 16, 32 or 64 the
+ * padded width, M = 5 or 8 the kernel's history capacity), 288 bytes of scalars and the copy of the box.
+ * _asks: how many problems asked for each kind of evaluation, accumulated over the calls, in the order clip-start,
+ * trial, cauchy, clip-next, first; once every problem has finished their sum is the sum of nfev over the problems. */
+typedef struct mi355_lbfgsb_ask_tell mi355_lbfgsb_ask_tell;
+int mi355_lbfgsb_ask_tell_create(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, const double* lower,
+                                 const double* upper, int64_t box_stride, int64_t B, const double* x0, void* stream,
+                                 mi355_lbfgsb_ask_tell** out);
+int mi355_lbfgsb_ask_tell_x(mi355_lbfgsb_ask_tell* handle, const double** x_eval);
+int mi355_lbfgsb_ask_tell_step(mi355_lbfgsb_ask_tell* handle, const double* f, const double* g, int64_t* active_host,
+                               void* stream);
+int mi355_lbfgsb_ask_tell_active(mi355_lbfgsb_ask_tell* handle, const int64_t** active_dev);
+int mi355_lbfgsb_ask_tell_results(mi355_lbfgsb_ask_tell* handle, double* x_out, double* f_out, double* g_out,
+                                  mi355_lbfgs_progress* progress_out, void* stream);
+int mi355_lbfgsb_ask_tell_destroy(mi355_lbfgsb_ask_tell* handle);
+/* counts_host: HOST, 5 counters; waits for `stream`. */
+int mi355_lbfgsb_ask_tell_asks(mi355_lbfgsb_ask_tell* handle, int64_t counts_host[5], void* stream);
+
 /* Duration in ms of the most recent solve kernel on this context, measured with
  * HIP events recorded on the launch stream; blocks until that kernel finished. */
 int mi355_lbfgs_last_kernel_ms(mi355_lbfgs_ctx* ctx, float* ms);
