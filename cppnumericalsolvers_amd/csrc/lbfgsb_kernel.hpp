@@ -606,8 +606,12 @@ __global__ __launch_bounds__(64, (E >= 4 || M > 5 || W > 16) ? 1 : 2) void lbfgs
         }
         const double tmax = seg_max<W>(bj < 0 ? -kMax : bt);
         const int jmax = -row_min_i<W>((bj >= 0 && bt == tmax) ? -bj : 0x7fffffff);
-        b = jmax;
-        t = tmax;
+        // Every t a NaN (a NaN gradient): no key compares, the sort leaves the entries in index order and the last one
+        // is coordinate n - 1 with its NaN for t.  The loop below does not run on it, but the drift after the loop
+        // (:424-427) does: the reference returns a NaN there even where x sits on a bound.
+        const bool unordered = jmax < 0;
+        b = unordered ? n - 1 : jmax;
+        t = unordered ? __builtin_nan("") : tmax;
         remaining = 1;
 #pragma unroll
         for (int e = 0; e < E; ++e) pending[e] = (sl * E + e == b);

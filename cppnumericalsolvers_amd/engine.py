@@ -1270,6 +1270,12 @@ class BatchedAugmentedLagrangian:
             capi.check(self.ctx._lib.mi355_auglag_minimize_batch(*head, *tail))
         return viol, kkt, prog
 
+    def last_launch(self):
+        """The dict of BatchedLbfgs.last_launch(): the record of the most recent launch of the inner-solver kernel on this
+        solver's context — the one launch of the fused loop; in the lock-step loop the last inner launch (after a
+        hand-over: the fused launch that took the survivors)."""
+        return BatchedLbfgs.last_launch(self)
+
     def evaluate_host(self, problem, x, lam=None, mu=None, penalty=0.0, term_constants=None):
         """Value and gradient of ToAugmentedLagrangian(problem, (lam, mu), penalty) at every row of x."""
         x, lam, mu, pen = self._state(problem, x, lam, mu, penalty)

@@ -38,9 +38,9 @@ loop at different times.
    condition_hessian on, dense Bfgs (n = 32 and n = 7), exact and relaxed-algebra Lbfgsb in a box that puts start
    coordinates on a bound, the workgroup kernel for n > 256, the ridge kernel on the matrix cores, and the lean kernel
    (against the general kernel and the twin).
-   NOT covered here: the augmented-Lagrangian drivers (their inner solves go through launch_solve / launch_lbfgsb, whose
-   queue and clamp the rows above exercise; their outer-loop state is not reset by these kernels) and the ridge Gram
-   pre-pass (not a persistent kernel; its solve is the general Lbfgs kernel).
+   The augmented-Lagrangian loops (the fused loop resets its outer-loop state inside these kernels; the lock-step loop
+   launches them through problem_map / count_dev) have a module of their own: tests/test_gpu_auglag_queue.py.
+   NOT covered here: the ridge Gram pre-pass (not a persistent kernel; its solve is the general Lbfgs kernel).
 """
 import os
 
