@@ -56,6 +56,8 @@ EXPORTED_SYMBOLS = [
     "mi355_lbfgs_minimize_batch_f32", "mi355_lbfgs_minimize_batch_f32_host", "mi355_lbfgs_eval_batch_f32",
     "mi355_lbfgs_ask_tell_create", "mi355_lbfgs_ask_tell_x", "mi355_lbfgs_ask_tell_step", "mi355_lbfgs_ask_tell_active",
     "mi355_lbfgs_ask_tell_results", "mi355_lbfgs_ask_tell_destroy",
+    "mi355_lbfgs_ask_tell_f32_create", "mi355_lbfgs_ask_tell_f32_x", "mi355_lbfgs_ask_tell_f32_step",
+    "mi355_lbfgs_ask_tell_f32_active", "mi355_lbfgs_ask_tell_f32_results", "mi355_lbfgs_ask_tell_f32_destroy",
     "mi355_lbfgsb_ask_tell_create", "mi355_lbfgsb_ask_tell_x", "mi355_lbfgsb_ask_tell_step", "mi355_lbfgsb_ask_tell_active",
     "mi355_lbfgsb_ask_tell_results", "mi355_lbfgsb_ask_tell_destroy", "mi355_lbfgsb_ask_tell_asks",
 ]
@@ -284,6 +286,12 @@ def _bind(L):
     L.mi355_lbfgs_ask_tell_active.argtypes = [vp, C.POINTER(vp)]
     L.mi355_lbfgs_ask_tell_results.argtypes = [vp, vp, vp, vp, vp, vp]
     L.mi355_lbfgs_ask_tell_destroy.argtypes = [vp]
+    L.mi355_lbfgs_ask_tell_f32_create.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, C.POINTER(vp)]
+    L.mi355_lbfgs_ask_tell_f32_x.argtypes = [vp, C.POINTER(vp)]
+    L.mi355_lbfgs_ask_tell_f32_step.argtypes = [vp, vp, vp, C.POINTER(C.c_int64), vp]
+    L.mi355_lbfgs_ask_tell_f32_active.argtypes = [vp, C.POINTER(vp)]
+    L.mi355_lbfgs_ask_tell_f32_results.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.mi355_lbfgs_ask_tell_f32_destroy.argtypes = [vp]
     L.mi355_lbfgsb_ask_tell_create.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, C.c_int64, vp, vp, C.POINTER(vp)]
     L.mi355_lbfgsb_ask_tell_x.argtypes = [vp, C.POINTER(vp)]
     L.mi355_lbfgsb_ask_tell_step.argtypes = [vp, vp, vp, C.POINTER(C.c_int64), vp]

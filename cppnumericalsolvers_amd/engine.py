@@ -228,7 +228,9 @@ class BatchedLbfgs:
     dtype: torch.float64 (default: every computation in fp64) or torch.float32 — the native float path
         (mi355_lbfgs_minimize_batch_f32): `minimize` / `evaluate` take and return float32 CUDA tensors, `minimize_host`
         float32 numpy arrays; More-Thuente, exact arithmetic, Rosenbrock / DiagQuadratic, n <= 256.  What that path does
-        not build is refused by the library with its reason (EngineError).  Only this class takes float32.
+        not build is refused by the library with its reason (EngineError).  Only this class takes float32;
+        `minimize_callable` / `LbfgsAskTell` on it run the float ask/tell path (mi355_lbfgs_ask_tell_f32_*) on any
+        float32 objective the caller evaluates.
     """
 
     _entry = "mi355_lbfgs_minimize_batch"  # C-ABI entry point (subclasses: other solvers of the same shape)
@@ -419,9 +421,10 @@ class BatchedLbfgs:
 
     def minimize_callable(self, fn, x0, check_every=1, max_rounds=None):
         """Batched Solver::Minimize of an objective the CALLER evaluates (ask/tell, `LbfgsAskTell`): `fn(X)` takes the
-        [B, n] float64 CUDA tensor of the points to evaluate and returns (f [B], g [B, n]) — or f alone, and the gradient
+        [B, n] CUDA tensor of the points to evaluate (of the solver's dtype: float64, or float32 on the native float
+        path of BatchedLbfgs) and returns (f [B], g [B, n]) of that dtype — or f alone, and the gradient
         is then torch.autograd.grad(f.sum(), X) on a leaf that requires grad (the problems are independent, so the
-        sum's gradient is the per-problem gradient).  X is the solver's own buffer: read it, do not keep or write it.
+        sum's gradient is the per-problem gradient; in float32 autograd differentiates in float32).  X is the solver's own buffer: read it, do not keep or write it.
         check_every=k reads the active count back every k rounds (a round on a finished batch changes nothing);
         max_rounds: RuntimeError when the batch is still active after that many rounds.
         Returns (x, f, g, progress) like `minimize`."""
@@ -504,27 +507,29 @@ class LbfgsAskTell:
     the caller evaluates.  The solver state of all problems lives on the device; every `tell` runs one kernel that takes
     each problem to its next evaluation.
 
-        at = amd.LbfgsAskTell(solver, x0)          # solver: a float64 BatchedLbfgs (m, stopping_progress, mapping)
+        at = amd.LbfgsAskTell(solver, x0)          # solver: a BatchedLbfgs (m, stopping_progress, mapping, dtype)
         while at.tell(*my_value_and_gradient(at.x)) > 0:
             pass
         x, f, g, progress = at.results()
 
     .x: the [B, n] float64 tensor VIEW of the evaluation buffer (no copy; valid until close()); rows of finished
-    problems hold their returned x, and what is handed back for them is never read.  A solver configured with what the
+    problems hold their returned x, and what is handed back for them is never read.  A solver built with
+    dtype=torch.float32 runs the native float path (mi355_lbfgs_ask_tell_f32_*): x0, .x, f, g and the results are
+    float32 then, and a tensor of the other dtype is a ValueError in both directions.  A solver configured with what the
     path does not build (Hager-Zhang, arithmetic="fma", y history in registers, condition_hessian) raises the
     library's message (EngineError).  Everything runs on the current stream of the solver's device."""
 
     _prefix = "mi355_lbfgs_ask_tell_"
 
+    _prefix_f32 = "mi355_lbfgs_ask_tell_f32_"   # the handle type of a float32 solver
+
     def _call(self, name, *args):
-        capi.check(getattr(self._lib, self._prefix + name)(*args))
+        capi.check(getattr(self._lib, (self._prefix_f32 if self._f32 else self._prefix) + name)(*args))
 
     def _check_solver(self, solver):
         if type(solver) is not BatchedLbfgs:
             raise TypeError("LbfgsAskTell takes a BatchedLbfgs (BatchedLbfgsb has LbfgsbAskTell; the other solvers have "
                             "no ask/tell form)")
-        if solver._f32:
-            raise ValueError("LbfgsAskTell computes in float64: the solver was built with dtype=torch.float32")
 
     def _create(self, solver, d, x0, h):
         self._call("create", solver.ctx.handle, C.byref(d), self.B, x0.data_ptr(), solver._stream(), C.byref(h))
@@ -533,8 +538,12 @@ class LbfgsAskTell:
         self._h = None
         self._check_solver(solver)
         torch = solver._torch
-        if x0.dtype != torch.float64 or x0.dim() != 2 or not x0.is_cuda:
-            raise ValueError("x0 must be a [B, n] float64 CUDA tensor")
+        self._f32 = bool(solver._f32)
+        self._dtype = solver.dtype
+        self._dtype_name = "float32" if self._f32 else "float64"
+        if x0.dtype != self._dtype or x0.dim() != 2 or not x0.is_cuda:
+            raise ValueError("x0 must be a [B, n] %s CUDA tensor: the solver computes in %s"
+                             % (self._dtype_name, self._dtype_name))
         solver._on_device(x0, "x0")
         x0 = x0.contiguous()
         self.solver = solver
@@ -547,15 +556,16 @@ class LbfgsAskTell:
         self._h = h
         p = C.c_void_p()
         self._call("x", self._h, C.byref(p))
-        self.x = torch.as_tensor(_DeviceArray(p.value, (self.B, self.n), "<f8", self), device=solver.device) \
-            if self.B > 0 else torch.empty(0, self.n, dtype=torch.float64, device=solver.device)
+        self.x = torch.as_tensor(_DeviceArray(p.value, (self.B, self.n), "<f4" if self._f32 else "<f8", self),
+                                 device=solver.device) \
+            if self.B > 0 else torch.empty(0, self.n, dtype=self._dtype, device=solver.device)
         self._call("active", self._h, C.byref(p))
         self._active_dev = torch.as_tensor(_DeviceArray(p.value, (1,), "<i8", self), device=solver.device)
 
     def _rows(self, t, shape, what):
         torch = self.solver._torch
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_cuda:
-            raise ValueError("%s must be a %s float64 CUDA tensor" % (what, list(shape)))
+        if not isinstance(t, torch.Tensor) or t.dtype != self._dtype or tuple(t.shape) != shape or not t.is_cuda:
+            raise ValueError("%s must be a %s %s CUDA tensor" % (what, list(shape), self._dtype_name))
         self.solver._on_device(t, what)
         return t.detach().contiguous()
 
@@ -585,9 +595,9 @@ class LbfgsAskTell:
             raise RuntimeError("this %s is closed" % type(self).__name__)
         torch = self.solver._torch
         dev = self.solver.device
-        x = torch.empty(self.B, self.n, dtype=torch.float64, device=dev)
-        g = torch.empty(self.B, self.n, dtype=torch.float64, device=dev)
-        f = torch.empty(self.B, dtype=torch.float64, device=dev)
+        x = torch.empty(self.B, self.n, dtype=self._dtype, device=dev)
+        g = torch.empty(self.B, self.n, dtype=self._dtype, device=dev)
+        f = torch.empty(self.B, dtype=self._dtype, device=dev)
         prog = torch.empty(self.B * capi.PROGRESS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         self._call("results", self._h, x.data_ptr(), f.data_ptr(), g.data_ptr(), prog.data_ptr(), self.solver._stream())
         return x, f, g, prog

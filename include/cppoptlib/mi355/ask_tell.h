@@ -5,6 +5,8 @@
 //   LbfgsAskTell        RAII handle of one batched solve: Ask() is the device pointer of the points to evaluate
 //                       ([B][n], the same pointer for the handle's lifetime), Tell(f_dev, g_dev) hands the values and
 //                       gradients back and returns the number of problems still active, Results(...) copies the states.
+//   LbfgsAskTellF32     the same in native float (mi355_lbfgs_ask_tell_f32_*): float x0, points, values, gradients and
+//                       results — a float objective is evaluated in its own precision, never widened
 //   LbfgsbAskTell       the same for Lbfgsb<F, m, MoreThuente>: no box, one shared box, or one box per problem
 //                       (mi355_lbfgsb_ask_tell_*), plus Asks(), the count of every kind of evaluation asked for
 //   MinimizeBatchWith   the loop around either: evaluator(x_dev, f_dev, g_dev, B, n) is the user's — its own kernels,
@@ -46,6 +48,7 @@ inline mi355_lbfgs_desc AskTellDesc(int n, int m = 10, const mi355_lbfgs_stop* s
 
 class LbfgsAskTell {
  public:
+  using Scalar = double;
   // x0_dev: DEVICE [B][n].  stream: a hipStream_t (nullptr: the default stream) for this and every later call.
   LbfgsAskTell(std::shared_ptr<Context> context, const mi355_lbfgs_desc& desc, int64_t B, const double* x0_dev,
                void* stream = nullptr)
@@ -99,6 +102,66 @@ class LbfgsAskTell {
   int n_ = 0;
 };
 
+// ---- Lbfgs<F, m, MoreThuente> with ScalarType = float in the same form (mi355_lbfgs_ask_tell_f32_*) -----------------
+// Every device array is float; the desc is AskTellDesc's (its thresholds are converted to float once by the library).
+class LbfgsAskTellF32 {
+ public:
+  using Scalar = float;
+  // x0_dev: DEVICE [B][n] floats.  stream: a hipStream_t (nullptr: the default stream) for this and every later call.
+  LbfgsAskTellF32(std::shared_ptr<Context> context, const mi355_lbfgs_desc& desc, int64_t B, const float* x0_dev,
+                  void* stream = nullptr)
+      : context_(std::move(context)), stream_(stream), B_(B), n_(desc.n) {
+    if (!context_) Fail("LbfgsAskTellF32: null context");
+    Check(mi355_lbfgs_ask_tell_f32_create(context_->get(), &desc, B, x0_dev, stream_, &handle_),
+          "mi355_lbfgs_ask_tell_f32_create");
+    Check(mi355_lbfgs_ask_tell_f32_x(handle_, &x_), "mi355_lbfgs_ask_tell_f32_x");
+  }
+  ~LbfgsAskTellF32() { (void)mi355_lbfgs_ask_tell_f32_destroy(handle_); }
+  LbfgsAskTellF32(const LbfgsAskTellF32&) = delete;
+  LbfgsAskTellF32& operator=(const LbfgsAskTellF32&) = delete;
+  LbfgsAskTellF32(LbfgsAskTellF32&& other) noexcept
+      : context_(std::move(other.context_)), handle_(other.handle_), x_(other.x_), stream_(other.stream_), B_(other.B_),
+        n_(other.n_) {
+    other.handle_ = nullptr;
+  }
+  LbfgsAskTellF32& operator=(LbfgsAskTellF32&&) = delete;
+
+  // DEVICE [B][n]: the points to evaluate (rows of finished problems hold their returned x)
+  const float* Ask() const { return x_; }
+  // f_dev [B], g_dev [B][n]: the evaluation of Ask()'s rows.  Waits for the stream; returns the problems still active.
+  int64_t Tell(const float* f_dev, const float* g_dev) {
+    int64_t active = 0;
+    Check(mi355_lbfgs_ask_tell_f32_step(handle_, f_dev, g_dev, &active, stream_), "mi355_lbfgs_ask_tell_f32_step");
+    return active;
+  }
+  // ... without waiting: the count is behind ActiveDevice() once the stream has run the call
+  void TellAsync(const float* f_dev, const float* g_dev) {
+    Check(mi355_lbfgs_ask_tell_f32_step(handle_, f_dev, g_dev, nullptr, stream_), "mi355_lbfgs_ask_tell_f32_step");
+  }
+  const int64_t* ActiveDevice() const {
+    const int64_t* p = nullptr;
+    Check(mi355_lbfgs_ask_tell_f32_active(handle_, &p), "mi355_lbfgs_ask_tell_f32_active");
+    return p;
+  }
+  // The current iterate of every problem, its value, gradient and progress record into DEVICE arrays (any may be null);
+  // asynchronous on the stream.
+  void Results(float* x_dev, float* f_dev, float* g_dev, mi355_lbfgs_progress* progress_dev) const {
+    Check(mi355_lbfgs_ask_tell_f32_results(handle_, x_dev, f_dev, g_dev, progress_dev, stream_),
+          "mi355_lbfgs_ask_tell_f32_results");
+  }
+  int64_t batch() const { return B_; }
+  int dimension() const { return n_; }
+  void* stream() const { return stream_; }
+
+ private:
+  std::shared_ptr<Context> context_;
+  mi355_lbfgs_ask_tell_f32* handle_ = nullptr;
+  const float* x_ = nullptr;
+  void* stream_ = nullptr;
+  int64_t B_ = 0;
+  int n_ = 0;
+};
+
 // ---- Lbfgsb<F, m, MoreThuente> in the same form (mi355_lbfgsb_ask_tell_*): simple bounds on the parameters -------------
 // The fields of mi355_lbfgs_desc the path reads, with the reference's Lbfgsb defaults (m = 5, the default stopping
 // progress with f_delta = 2.22e-9 relative, lbfgsb.h:84-87); the mapping is the library's.
@@ -125,6 +188,7 @@ struct LbfgsbAsks {
 
 class LbfgsbAskTell {
  public:
+  using Scalar = double;
   // No box: the reference's default unbounded one.  x0_dev: DEVICE [B][n]; stream as for LbfgsAskTell.
   LbfgsbAskTell(std::shared_ptr<Context> context, const mi355_lbfgs_desc& desc, int64_t B, const double* x0_dev,
                 void* stream = nullptr)
@@ -197,9 +261,10 @@ class LbfgsbAskTell {
 // The loop: evaluate, tell, until no problem is active.  f_dev [B] and g_dev [B][n] are the caller's work arrays; the
 // evaluator must order its work on solve.stream().  max_rounds < 0: no limit; otherwise Fail() when the batch is still
 // active after that many rounds.  Returns the number of rounds (= evaluations of the batch).
-// Handle: LbfgsAskTell or LbfgsbAskTell.
+// Handle: LbfgsAskTell, LbfgsAskTellF32 or LbfgsbAskTell; the work arrays are of the handle's Scalar (double, float).
 template <class Evaluator, class Handle>
-int64_t MinimizeBatchWith(Evaluator&& evaluator, Handle& solve, double* f_dev, double* g_dev, int64_t max_rounds = -1) {
+int64_t MinimizeBatchWith(Evaluator&& evaluator, Handle& solve, typename Handle::Scalar* f_dev,
+                          typename Handle::Scalar* g_dev, int64_t max_rounds = -1) {
   int64_t rounds = 0;
   if (solve.batch() == 0) return rounds;
   while (true) {
@@ -223,6 +288,18 @@ int64_t MinimizeBatchWith(Evaluator&& evaluator, std::shared_ptr<Context> contex
   const int64_t rounds = MinimizeBatchWith(std::forward<Evaluator>(evaluator), solve, f_work_dev, g_work_dev, max_rounds);
   solve.Results(x_out, f_out, g_out, progress_out);
   return rounds;   // (the handle's destructor waits for the device: the results are in place)
+}
+
+// ... the same in native float (LbfgsAskTellF32)
+template <class Evaluator>
+int64_t MinimizeBatchWith(Evaluator&& evaluator, std::shared_ptr<Context> context, const mi355_lbfgs_desc& desc, int64_t B,
+                          const float* x0_dev, float* f_work_dev, float* g_work_dev, float* x_out, float* f_out,
+                          float* g_out, mi355_lbfgs_progress* progress_out, void* stream = nullptr,
+                          int64_t max_rounds = -1) {
+  LbfgsAskTellF32 solve(std::move(context), desc, B, x0_dev, stream);
+  const int64_t rounds = MinimizeBatchWith(std::forward<Evaluator>(evaluator), solve, f_work_dev, g_work_dev, max_rounds);
+  solve.Results(x_out, f_out, g_out, progress_out);
+  return rounds;
 }
 
 }  // namespace cppoptlib::mi355

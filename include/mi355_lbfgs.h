@@ -701,6 +701,31 @@ int mi355_lbfgs_ask_tell_results(mi355_lbfgs_ask_tell* handle, double* x_out, do
                                  mi355_lbfgs_progress* progress_out, void* stream);
 int mi355_lbfgs_ask_tell_destroy(mi355_lbfgs_ask_tell* handle);
 
+/* ---- ask/tell L-BFGS in native float: float objectives the CALLER evaluates -----------------------------------------
+ * Lbfgs<F, m, MoreThuente>::Minimize with ScalarType = float in the protocol of mi355_lbfgs_ask_tell_*: a handle type of
+ * its own, float arrays where the fp64 functions take double arrays, the same meaning of every call.  The arithmetic is
+ * that of mi355_lbfgs_minimize_batch_f32 (every operation a float operation, every constant the reference's double
+ * literal rounded once, the stop record's thresholds converted once), so a callback that evaluates with
+ * mi355_lbfgs_eval_batch_f32 reproduces mi355_lbfgs_minimize_batch_f32 bit for bit (x, f, g and every field of the
+ * progress record, whose three doubles are the float values widened; a NaN among them is the canonical quiet NaN).
+ * Of desc: n, m, stop, lanes_per_problem and elems_per_lane are read (the mappings and the 0 / 0 rule of
+ * mi355_lbfgs_ask_tell_*); objective and the parameter fields are ignored.  MI355_ERR_UNSUPPORTED with a message that
+ * starts "Lbfgs ask/tell f32" and names the reason, before anything is allocated or launched, for: Hager-Zhang,
+ * MI355_ARITH_FMA, MI355_HISTORY_Y_IN_REGISTERS, hessian_from_functor, hessian_diagonal, hessian_condition_stop > 0, a
+ * trace, per_problem_data, n > 256, m > MI355_LBFGS_MAX_M, a mapping that is not built.  Null arguments:
+ * MI355_ERR_INVALID_ARGUMENT; _destroy(NULL) returns 0; B = 0 is valid.  Device memory per problem: (3 + 2 m) P + n
+ * floats (P = lanes x coordinates per lane) and 296 bytes of scalars. */
+typedef struct mi355_lbfgs_ask_tell_f32 mi355_lbfgs_ask_tell_f32;
+int mi355_lbfgs_ask_tell_f32_create(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const float* x0,
+                                    void* stream, mi355_lbfgs_ask_tell_f32** out);
+int mi355_lbfgs_ask_tell_f32_x(mi355_lbfgs_ask_tell_f32* handle, const float** x_eval);
+int mi355_lbfgs_ask_tell_f32_step(mi355_lbfgs_ask_tell_f32* handle, const float* f, const float* g,
+                                  int64_t* active_host, void* stream);
+int mi355_lbfgs_ask_tell_f32_active(mi355_lbfgs_ask_tell_f32* handle, const int64_t** active_dev);
+int mi355_lbfgs_ask_tell_f32_results(mi355_lbfgs_ask_tell_f32* handle, float* x_out, float* f_out, float* g_out,
+                                     mi355_lbfgs_progress* progress_out, void* stream);
+int mi355_lbfgs_ask_tell_f32_destroy(mi355_lbfgs_ask_tell_f32* handle);
+
 /* ---- ask/tell (reverse communication) L-BFGS-B: bounds for objectives the CALLER evaluates -------------------------
  * Lbfgsb<F, m, MoreThuente>::Minimize (solver/lbfgsb.h:141-292) in the same protocol as mi355_lbfgs_ask_tell_*: the
  * batched counterpart of "B small problems, my loss in torch, simple bounds on the parameters".  The iteration is cut at
