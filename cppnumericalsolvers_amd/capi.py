@@ -280,24 +280,15 @@ def _bind(L):
     L.mi355_lbfgs_minimize_batch_f32.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mi355_lbfgs_minimize_batch_f32_host.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp]
     L.mi355_lbfgs_eval_batch_f32.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp]
-    L.mi355_lbfgs_ask_tell_create.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, C.POINTER(vp)]
-    L.mi355_lbfgs_ask_tell_x.argtypes = [vp, C.POINTER(vp)]
-    L.mi355_lbfgs_ask_tell_step.argtypes = [vp, vp, vp, C.POINTER(C.c_int64), vp]
-    L.mi355_lbfgs_ask_tell_active.argtypes = [vp, C.POINTER(vp)]
-    L.mi355_lbfgs_ask_tell_results.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.mi355_lbfgs_ask_tell_destroy.argtypes = [vp]
-    L.mi355_lbfgs_ask_tell_f32_create.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, C.POINTER(vp)]
-    L.mi355_lbfgs_ask_tell_f32_x.argtypes = [vp, C.POINTER(vp)]
-    L.mi355_lbfgs_ask_tell_f32_step.argtypes = [vp, vp, vp, C.POINTER(C.c_int64), vp]
-    L.mi355_lbfgs_ask_tell_f32_active.argtypes = [vp, C.POINTER(vp)]
-    L.mi355_lbfgs_ask_tell_f32_results.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.mi355_lbfgs_ask_tell_f32_destroy.argtypes = [vp]
+    # the three ask/tell handles share their signatures but for the box arguments of Lbfgsb's create, and its _asks
+    for prefix in ("mi355_lbfgs_ask_tell_", "mi355_lbfgs_ask_tell_f32_", "mi355_lbfgsb_ask_tell_"):
+        getattr(L, prefix + "create").argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, C.POINTER(vp)]
+        getattr(L, prefix + "x").argtypes = [vp, C.POINTER(vp)]
+        getattr(L, prefix + "step").argtypes = [vp, vp, vp, C.POINTER(C.c_int64), vp]
+        getattr(L, prefix + "active").argtypes = [vp, C.POINTER(vp)]
+        getattr(L, prefix + "results").argtypes = [vp, vp, vp, vp, vp, vp]
+        getattr(L, prefix + "destroy").argtypes = [vp]
     L.mi355_lbfgsb_ask_tell_create.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, C.c_int64, vp, vp, C.POINTER(vp)]
-    L.mi355_lbfgsb_ask_tell_x.argtypes = [vp, C.POINTER(vp)]
-    L.mi355_lbfgsb_ask_tell_step.argtypes = [vp, vp, vp, C.POINTER(C.c_int64), vp]
-    L.mi355_lbfgsb_ask_tell_active.argtypes = [vp, C.POINTER(vp)]
-    L.mi355_lbfgsb_ask_tell_results.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.mi355_lbfgsb_ask_tell_destroy.argtypes = [vp]
     L.mi355_lbfgsb_ask_tell_asks.argtypes = [vp, C.POINTER(C.c_int64), vp]
     L.mi355_bfgs_minimize_batch.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mi355_bfgs_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp]

@@ -1,201 +1,254 @@
-// ask_tell_entry.hip — the C entry points of the ask/tell (reverse communication) L-BFGS (include/mi355_lbfgs.h,
-// mi355_lbfgs_ask_tell_*): the refusals, the solve handle with its one device allocation, and the calls into
-// dispatch_lbfgs_ask_tell.hip.  No kernel lives here.
-#include <new>
-
-#include "engine_internal.hpp"
+// ask_tell_entry.hip — the C entry points of the three ask/tell (reverse communication) paths (include/mi355_lbfgs.h):
+// mi355_lbfgs_ask_tell_* (Lbfgs in double), mi355_lbfgs_ask_tell_f32_* (Lbfgs in float) and mi355_lbfgsb_ask_tell_*
+// (Lbfgsb).  Each path is its traits, its handle struct, its own refusals and its C functions; the rest —
+// the shared refusals, the one device allocation and its layout, the bodies of the entry points — is ask_tell_host.hpp.
+// The kernels are behind dispatch_lbfgs_ask_tell.hip, dispatch_lbfgs_ask_tell_f32.hip and dispatch_lbfgsb_ask_tell.hip.
+#include "ask_tell_host.hpp"
 #include "lbfgs_ask_tell_config.hpp"
+#include "lbfgs_ask_tell_f32_config.hpp"
+#include "lbfgsb_ask_tell_config.hpp"
 
 using namespace mi355;
+namespace host = mi355::ask_tell_host;
 
-// One solve in flight: the state of all B problems in ONE device allocation
-//   [ x_eval B n | vectors B (3 + 2m) P | scalars B | active counter ]
-struct mi355_lbfgs_ask_tell {
-  mi355_lbfgs_ctx* ctx = nullptr;
-  char* block = nullptr;
-  size_t bytes = 0;
-  double* x_eval = nullptr;
-  double* vectors = nullptr;
-  ask_tell::Scalars* scalars = nullptr;
-  unsigned long long* active = nullptr;
-  int64_t B = 0;
-  int n = 0, m = 0, W = 0, E = 0;
-  mi355_lbfgs_stop stop;
+namespace mi355 {
+namespace ask_tell_host {
+
+struct LbfgsPath {
+  using Scalar = double;
+  using Scalars = ask_tell::Scalars;
+  using Args = ask_tell::Args;
+  using ResultArgs = ask_tell::ResultArgs;
+  static long long row(int m, int P) { return ask_tell::row_doubles(m, P); }
+  static constexpr auto step = &dispatch_ask_tell_step;
+  static constexpr auto results = &dispatch_ask_tell_results;
+  static constexpr const char* kPrefix = "Lbfgs ask/tell";
+  static constexpr const char* kWhat = "ask/tell";
+  static constexpr bool kRefusesLargeM = false;  // validate() words the m limit
+};
+
+struct LbfgsF32Path {
+  using Scalar = float;
+  using Scalars = ask_tell_f32::Scalars;
+  using Args = ask_tell_f32::Args;
+  using ResultArgs = ask_tell_f32::ResultArgs;
+  static long long row(int m, int P) { return ask_tell_f32::row_floats(m, P); }
+  static constexpr auto step = &dispatch_ask_tell_f32_step;
+  static constexpr auto results = &dispatch_ask_tell_f32_results;
+  static constexpr const char* kPrefix = "Lbfgs ask/tell f32";
+  static constexpr const char* kWhat = "ask/tell f32";
+  static constexpr bool kRefusesLargeM = true;
+};
+
+struct LbfgsbPath {
+  using Scalar = double;
+  using Scalars = ask_tell_box::Scalars;
+  using Args = ask_tell_box::Args;
+  using ResultArgs = ask_tell_box::ResultArgs;
+  static long long row(int m, int P) { return ask_tell_box::row_doubles(m, ask_tell_box_capacity(m), P); }
+  static int step(mi355_lbfgs_ctx* ctx, int, int E, const Args& a, hipStream_t stream) {  // (W is kLanes)
+    return dispatch_ask_tell_box_step(ctx, E, a, stream);
+  }
+  static constexpr auto results = &dispatch_ask_tell_box_results;
+  static constexpr const char* kPrefix = "Lbfgsb ask/tell";
+  static constexpr const char* kWhat = "ask/tell";
+};
+
+}  // namespace ask_tell_host
+}  // namespace mi355
+
+struct mi355_lbfgs_ask_tell : host::Handle<host::LbfgsPath> {};
+
+struct mi355_lbfgs_ask_tell_f32 : host::Handle<host::LbfgsF32Path> {
+  // static_cast<float> of the stop record's thresholds, converted once per call
+  void finish_args(ask_tell_f32::Args& a) const {
+    a.stop_x_delta = static_cast<float>(stop.x_delta);
+    a.stop_f_delta = static_cast<float>(stop.f_delta);
+    a.stop_gradient_norm = static_cast<float>(stop.gradient_norm);
+    a.stop_past_delta = static_cast<float>(stop.past_delta);
+  }
+};
+
+// extras: the handle's copy of the box, lower then upper (n each, or B n each); counters: active, asks[5], the NaN flag
+struct mi355_lbfgsb_ask_tell : host::Handle<host::LbfgsbPath> {
+  double* lower = nullptr;
+  double* upper = nullptr;
+  unsigned long long* asks = nullptr;
+  int* nan_flag = nullptr;
+  long long box_stride = 0;  // of the handle's copy: 0 (one box) or n
+  static constexpr int kCounterWords = 1 + ask_tell_box::kAskKinds + 1;
+  size_t box_doubles() const { return static_cast<size_t>(n) * ((box_stride != 0) ? static_cast<size_t>(B) : 1); }
+  size_t extra_bytes() const { return 2 * box_doubles() * sizeof(double); }
+  void place_extras(char* extras) {
+    lower = reinterpret_cast<double*>(extras);
+    upper = lower + box_doubles();
+    asks = active + 1;
+    nan_flag = reinterpret_cast<int*>(asks + ask_tell_box::kAskKinds);
+  }
+  void finish_args(ask_tell_box::Args& a) const {
+    a.lower = lower;
+    a.upper = upper;
+    a.box_stride = box_stride;
+    a.asks = asks;
+  }
 };
 
 namespace {
 
-int refuse(const char* text) { return fail(MI355_ERR_UNSUPPORTED, std::string("Lbfgs ask/tell") + text); }
-
-// Everything checked before the device is touched: the refusals (MI355_ERR_UNSUPPORTED, with the reason), then
-// validate()'s argument checks on the fields this path reads (the objective and its parameters are not among them: the
-// caller evaluates), then the lane mapping.
-int check(const mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, int& W, int& E) {
-  if (!ctx) return fail(MI355_ERR_INVALID_ARGUMENT, "null context");
-  if (!desc) return fail(MI355_ERR_INVALID_ARGUMENT, "null desc");
-  if (desc->linesearch == MI355_LS_HAGER_ZHANG)
-    return refuse(" is built with the More-Thuente line search only (no Hager-Zhang)");
-  if (desc->arithmetic == MI355_ARITH_FMA) return refuse(" is built for the exact arithmetic only (no MI355_ARITH_FMA)");
-  if (desc->history_placement == MI355_HISTORY_Y_IN_REGISTERS)
-    return refuse(" keeps the history in device memory between calls (no MI355_HISTORY_Y_IN_REGISTERS)");
-  if (desc->hessian_from_functor) return refuse(" is built for First-mode functions (no hessian_from_functor)");
-  if (desc->hessian_diagonal != nullptr) return refuse(" is built for First-mode functions (no hessian_diagonal)");
-  if (desc->hessian_condition_stop > 0.0)
-    return refuse(" is built for First-mode functions (no hessian_condition_stop)");
-  if (desc->trace != nullptr) return refuse(" records no per-iteration trace");
-  if (desc->per_problem_data != nullptr)
-    return refuse(" takes no per_problem_data: the caller's evaluation holds the problem's data");
-  if (desc->n > MI355_LBFGS_MAX_N) return refuse(" is built for n <= 256");
-  mi355_lbfgs_desc read = *desc;  // the objective is the caller's: its id and parameter fields are not looked at
-  read.objective = MI355_OBJ_ROSENBROCK;
-  read.objective_params = nullptr;
-  read.n_params = 0;
-  read.per_problem_stride = 0;
-  const int rc = validate(ctx, &read, B);
+// Lbfgsb's own refusals around the shared ones, then the box arguments
+int check_box(const mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const double* lower,
+              const double* upper, int64_t box_stride) {
+  using T = host::LbfgsbPath;
+  const int rc = host::check_common<T>(
+      ctx, desc, B,
+      [&] {
+        if (desc->arithmetic == MI355_ARITH_FMA)
+          return host::refuse<T>(" is built for the reference-order arithmetic only (no MI355_ARITH_FMA: the relaxed algebra has "
+                                 "no ask/tell form)");
+        if (desc->m > 8) return host::refuse<T>(" is built for m <= 8 (m = 9, 10 take 32 lanes per problem)");
+        if (desc->n > 64) return host::refuse<T>(" is built for n <= 64");
+        return static_cast<int>(MI355_OK);
+      },
+      [&] {
+        if (desc->hessian_from_functor) return host::refuse<T>(": Lbfgsb has no preconditioned path (no hessian_from_functor)");
+        if (desc->hessian_diagonal != nullptr) return host::refuse<T>(": Lbfgsb has no preconditioned path (no hessian_diagonal)");
+        if (desc->hessian_condition_stop > 0.0) return host::refuse<T>(" computes no Hessian (no hessian_condition_stop)");
+        if (desc->lanes_per_problem != 0 || desc->elems_per_lane != 0 || desc->history_placement != 0)
+          return host::refuse<T>(" chooses its own mapping: leave lanes_per_problem, elems_per_lane and history_placement 0");
+        return static_cast<int>(MI355_OK);
+      });
   if (rc != MI355_OK) return rc;
-  W = desc->lanes_per_problem;
-  E = desc->elems_per_lane;
-  if (W == 0 && E == 0) {
-    W = 8;
-    while (W < desc->n && W < 64) W <<= 1;
-  }
-  if (E == 0 && (W == 8 || W == 16 || W == 32 || W == 64)) E = (desc->n <= W) ? 1 : ((desc->n <= 2 * W) ? 2 : 4);
-  const bool built = ((W == 8 || W == 16 || W == 32 || W == 64) && E == 1) || (W == 64 && (E == 2 || E == 4));
-  if (!built || W * E < desc->n)
-    return refuse(": this mapping is not built; it must cover n with 8, 16, 32 or 64 lanes at one coordinate per lane, "
-                  "or 64 lanes at two or four");
+  if ((lower == nullptr) != (upper == nullptr))
+    return fail(MI355_ERR_INVALID_ARGUMENT, "lower and upper must both be given or both be NULL");
+  if (box_stride != 0 && !lower)
+    return fail(MI355_ERR_INVALID_ARGUMENT, "per-problem bounds: lower and upper are required");
+  if (box_stride != 0 && box_stride < desc->n)
+    return fail(MI355_ERR_INVALID_ARGUMENT, "per-problem bounds: box_stride must be >= n (0: one shared box)");
   return MI355_OK;
 }
 
-ask_tell::Args step_args(const mi355_lbfgs_ask_tell* h, const double* f, const double* g) {
-  ask_tell::Args a;
-  a.vectors = h->vectors;
-  a.scalars = h->scalars;
-  a.x_eval = h->x_eval;
-  a.f = f;
-  a.g = g;
-  a.active = h->active;
-  a.B = h->B;
-  a.n = h->n;
-  a.m = h->m;
-  a.stop = h->stop;
-  return a;
+// x0 into the state, the caller's box (or the reference's default one) into the handle's copy.  A NaN bound makes the
+// breakpoint order of the Cauchy search undefined in the reference as well (the check of
+// mi355_lbfgsb_minimize_batch_host, taken on the handle's copy: the caller's arrays are device memory here).
+int init_box(mi355_lbfgsb_ask_tell& h, const double* x0, const double* lower, const double* upper, int64_t box_stride,
+             long long row, hipStream_t stream) {
+  ask_tell_box::InitArgs ia;
+  ia.vectors = h.vectors;
+  ia.scalars = h.scalars;
+  ia.x_eval = h.x_eval;
+  ia.x0 = x0;
+  ia.lower = h.lower;
+  ia.upper = h.upper;
+  ia.lower_in = lower;
+  ia.upper_in = upper;
+  ia.box_stride_in = box_stride;
+  ia.asks = h.asks;
+  ia.nan_flag = h.nan_flag;
+  ia.B = h.B;
+  ia.row = row;
+  ia.n = h.n;
+  const int rc = dispatch_ask_tell_box_init(ia, stream);
+  if (rc != MI355_OK || lower == nullptr) return rc;
+  int flag = 0;
+  hipError_t he = hipMemcpyAsync(&flag, h.nan_flag, sizeof(flag), hipMemcpyDeviceToHost, stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(stream);
+  if (he != hipSuccess) return fail(MI355_ERR_HIP, std::string("ask/tell box check: ") + hipGetErrorString(he));
+  if (flag != 0) return fail(MI355_ERR_INVALID_ARGUMENT, "NaN bound");
+  return MI355_OK;
 }
 
 }  // namespace
 
 extern "C" {
 
+// ---- Lbfgs in double --------------------------------------------------------------------------------------------------
 int mi355_lbfgs_ask_tell_create(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const double* x0,
-                                void* stream_, mi355_lbfgs_ask_tell** out) {
-  if (!out) return fail(MI355_ERR_INVALID_ARGUMENT, "null handle pointer");
-  *out = nullptr;
-  int W = 0, E = 0;
-  const int rc = check(ctx, desc, B, W, E);
-  if (rc != MI355_OK) return rc;
-  if (B > 0 && !x0) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  MI355_ENTER_DEVICE(ctx);
-  mi355_lbfgs_ask_tell* h = new (std::nothrow) mi355_lbfgs_ask_tell;
-  if (!h) return fail(MI355_ERR_HIP, "ask/tell handle allocation failed");
-  h->ctx = ctx;
-  h->B = B;
-  h->n = desc->n;
-  h->m = desc->m;
-  h->W = W;
-  h->E = E;
-  h->stop = desc->stop;
-  const size_t row = static_cast<size_t>(ask_tell::row_doubles(h->m, W * E));
-  const size_t eval_bytes = static_cast<size_t>(B) * h->n * sizeof(double);
-  const size_t vector_bytes = static_cast<size_t>(B) * row * sizeof(double);
-  const size_t scalar_bytes = static_cast<size_t>(B) * sizeof(ask_tell::Scalars);
-  h->bytes = eval_bytes + vector_bytes + scalar_bytes + sizeof(unsigned long long);
-  const hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->block), h->bytes);
-  if (e != hipSuccess) {
-    const size_t asked = h->bytes;
-    delete h;
-    return fail(MI355_ERR_HIP, "hipMalloc of the ask/tell state (" + std::to_string(asked) + " bytes): " + hipGetErrorString(e));
-  }
-  h->x_eval = reinterpret_cast<double*>(h->block);
-  h->vectors = reinterpret_cast<double*>(h->block + eval_bytes);
-  h->scalars = reinterpret_cast<ask_tell::Scalars*>(h->block + eval_bytes + vector_bytes);
-  h->active = reinterpret_cast<unsigned long long*>(h->block + eval_bytes + vector_bytes + scalar_bytes);
-  int status = MI355_OK;
-  // padding, rings and scalars zero (phase: first evaluation pending); every problem counts as active
-  hipError_t he = hipMemsetAsync(h->block + eval_bytes, 0, vector_bytes + scalar_bytes, stream);
-  if (he == hipSuccess) {
-    const unsigned long long all = static_cast<unsigned long long>(B);
-    he = hipMemcpyAsync(h->active, &all, sizeof(all), hipMemcpyHostToDevice, stream);
-  }
-  if (he != hipSuccess) status = fail(MI355_ERR_HIP, std::string("ask/tell state initialisation: ") + hipGetErrorString(he));
-  if (status == MI355_OK && B > 0) status = dispatch_ask_tell_init(step_args(h, nullptr, nullptr), x0, static_cast<long long>(row), stream);
-  if (status != MI355_OK) {
-    (void)hipFree(h->block);
-    delete h;
-    return status;
-  }
-  *out = h;
-  return MI355_OK;
+                                void* stream, mi355_lbfgs_ask_tell** out) {
+  return host::create(
+      ctx, desc, B, x0, stream, out,
+      [&](mi355_lbfgs_ask_tell& h) { return host::check_lbfgs<host::LbfgsPath>(ctx, desc, B, h.W, h.E); },
+      [&](mi355_lbfgs_ask_tell& h, long long row, hipStream_t s) {
+        return dispatch_ask_tell_init(host::step_args(&h, nullptr, nullptr), x0, row, s);
+      });
 }
-
-int mi355_lbfgs_ask_tell_x(mi355_lbfgs_ask_tell* handle, const double** x_eval) {
-  if (!handle || !x_eval) return fail(MI355_ERR_INVALID_ARGUMENT, "null argument");
-  *x_eval = handle->x_eval;
-  return MI355_OK;
-}
-
+int mi355_lbfgs_ask_tell_x(mi355_lbfgs_ask_tell* handle, const double** x_eval) { return host::x(handle, x_eval); }
 int mi355_lbfgs_ask_tell_step(mi355_lbfgs_ask_tell* handle, const double* f, const double* g, int64_t* active_host,
-                              void* stream_) {
-  if (!handle) return fail(MI355_ERR_INVALID_ARGUMENT, "null handle");
-  if (handle->B > 0 && (!f || !g)) return fail(MI355_ERR_INVALID_ARGUMENT, "null f / g");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  MI355_ENTER_DEVICE(handle->ctx);
-  if (handle->B > 0) {
-    const int rc = dispatch_ask_tell_step(handle->ctx, handle->W, handle->E, step_args(handle, f, g), stream);
-    if (rc != MI355_OK) return rc;
-  }
-  if (active_host) {
-    unsigned long long count = 0;
-    HIP_TRY(hipMemcpyAsync(&count, handle->active, sizeof(count), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    *active_host = static_cast<int64_t>(count);
-  }
-  return MI355_OK;
+                              void* stream) {
+  return host::step(handle, f, g, active_host, stream);
 }
-
 int mi355_lbfgs_ask_tell_active(mi355_lbfgs_ask_tell* handle, const int64_t** active_dev) {
-  if (!handle || !active_dev) return fail(MI355_ERR_INVALID_ARGUMENT, "null argument");
-  *active_dev = reinterpret_cast<const int64_t*>(handle->active);
-  return MI355_OK;
+  return host::active(handle, active_dev);
 }
-
 int mi355_lbfgs_ask_tell_results(mi355_lbfgs_ask_tell* handle, double* x_out, double* f_out, double* g_out,
-                                 mi355_lbfgs_progress* progress_out, void* stream_) {
-  if (!handle) return fail(MI355_ERR_INVALID_ARGUMENT, "null handle");
-  if (handle->B == 0) return MI355_OK;
+                                 mi355_lbfgs_progress* progress_out, void* stream) {
+  return host::results(handle, x_out, f_out, g_out, progress_out, stream);
+}
+int mi355_lbfgs_ask_tell_destroy(mi355_lbfgs_ask_tell* handle) { return host::destroy(handle); }
+
+// ---- Lbfgs in float ---------------------------------------------------------------------------------------------------
+int mi355_lbfgs_ask_tell_f32_create(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const float* x0,
+                                    void* stream, mi355_lbfgs_ask_tell_f32** out) {
+  return host::create(
+      ctx, desc, B, x0, stream, out,
+      [&](mi355_lbfgs_ask_tell_f32& h) { return host::check_lbfgs<host::LbfgsF32Path>(ctx, desc, B, h.W, h.E); },
+      [&](mi355_lbfgs_ask_tell_f32& h, long long row, hipStream_t s) {
+        return dispatch_ask_tell_f32_init(host::step_args(&h, nullptr, nullptr), x0, row, s);
+      });
+}
+int mi355_lbfgs_ask_tell_f32_x(mi355_lbfgs_ask_tell_f32* handle, const float** x_eval) { return host::x(handle, x_eval); }
+int mi355_lbfgs_ask_tell_f32_step(mi355_lbfgs_ask_tell_f32* handle, const float* f, const float* g,
+                                  int64_t* active_host, void* stream) {
+  return host::step(handle, f, g, active_host, stream);
+}
+int mi355_lbfgs_ask_tell_f32_active(mi355_lbfgs_ask_tell_f32* handle, const int64_t** active_dev) {
+  return host::active(handle, active_dev);
+}
+int mi355_lbfgs_ask_tell_f32_results(mi355_lbfgs_ask_tell_f32* handle, float* x_out, float* f_out, float* g_out,
+                                     mi355_lbfgs_progress* progress_out, void* stream) {
+  return host::results(handle, x_out, f_out, g_out, progress_out, stream);
+}
+int mi355_lbfgs_ask_tell_f32_destroy(mi355_lbfgs_ask_tell_f32* handle) { return host::destroy(handle); }
+
+// ---- Lbfgsb -----------------------------------------------------------------------------------------------------------
+int mi355_lbfgsb_ask_tell_create(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, const double* lower,
+                                 const double* upper, int64_t box_stride, int64_t B, const double* x0, void* stream,
+                                 mi355_lbfgsb_ask_tell** out) {
+  return host::create(
+      ctx, desc, B, x0, stream, out,
+      [&](mi355_lbfgsb_ask_tell& h) {
+        const int rc = check_box(ctx, desc, B, lower, upper, box_stride);
+        if (rc != MI355_OK) return rc;
+        h.W = ask_tell_box::kLanes;
+        h.E = (desc->n <= 16) ? 1 : ((desc->n <= 32) ? 2 : 4);
+        h.box_stride = (box_stride != 0) ? desc->n : 0;
+        return static_cast<int>(MI355_OK);
+      },
+      [&](mi355_lbfgsb_ask_tell& h, long long row, hipStream_t s) {
+        return init_box(h, x0, lower, upper, box_stride, row, s);
+      });
+}
+int mi355_lbfgsb_ask_tell_x(mi355_lbfgsb_ask_tell* handle, const double** x_eval) { return host::x(handle, x_eval); }
+int mi355_lbfgsb_ask_tell_step(mi355_lbfgsb_ask_tell* handle, const double* f, const double* g, int64_t* active_host,
+                               void* stream) {
+  return host::step(handle, f, g, active_host, stream);
+}
+int mi355_lbfgsb_ask_tell_active(mi355_lbfgsb_ask_tell* handle, const int64_t** active_dev) {
+  return host::active(handle, active_dev);
+}
+int mi355_lbfgsb_ask_tell_asks(mi355_lbfgsb_ask_tell* handle, int64_t* counts_host, void* stream_) {
+  if (!handle || !counts_host) return fail(MI355_ERR_INVALID_ARGUMENT, "null argument");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   MI355_ENTER_DEVICE(handle->ctx);
-  ask_tell::ResultArgs r;
-  r.vectors = handle->vectors;
-  r.scalars = handle->scalars;
-  r.x_out = x_out;
-  r.f_out = f_out;
-  r.g_out = g_out;
-  r.progress_out = progress_out;
-  r.B = handle->B;
-  r.row_p = static_cast<long long>(handle->W) * handle->E;
-  r.row = ask_tell::row_doubles(handle->m, handle->W * handle->E);
-  r.n = handle->n;
-  return dispatch_ask_tell_results(r, stream);
-}
-
-int mi355_lbfgs_ask_tell_destroy(mi355_lbfgs_ask_tell* handle) {
-  if (!handle) return MI355_OK;
-  MI355_ENTER_DEVICE(handle->ctx);
-  const hipError_t e = hipFree(handle->block);  // (waits for the device: no kernel still reads the state)
-  delete handle;
-  if (e != hipSuccess) return fail(MI355_ERR_HIP, std::string("hipFree of the ask/tell state: ") + hipGetErrorString(e));
+  unsigned long long counts[ask_tell_box::kAskKinds];
+  HIP_TRY(hipMemcpyAsync(counts, handle->asks, sizeof(counts), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  for (int i = 0; i < ask_tell_box::kAskKinds; ++i) counts_host[i] = static_cast<int64_t>(counts[i]);
   return MI355_OK;
 }
+int mi355_lbfgsb_ask_tell_results(mi355_lbfgsb_ask_tell* handle, double* x_out, double* f_out, double* g_out,
+                                  mi355_lbfgs_progress* progress_out, void* stream) {
+  return host::results(handle, x_out, f_out, g_out, progress_out, stream);
+}
+int mi355_lbfgsb_ask_tell_destroy(mi355_lbfgsb_ask_tell* handle) { return host::destroy(handle); }
 
 }  // extern "C"

@@ -1,0 +1,318 @@
+// ask_tell_host.hpp — the host code the three ask/tell (reverse communication) paths share: Lbfgs in double
+// (mi355_lbfgs_ask_tell_*), Lbfgs in float (mi355_lbfgs_ask_tell_f32_*) and Lbfgsb (mi355_lbfgsb_ask_tell_*).  The
+// handle base with its one device allocation, the refusals common to the three, the entry-point bodies
+// (ask_tell_entry.hip turns them into the C functions) and the two launches of the dispatch units.  No kernel lives here.
+//
+// A path is described by a traits struct T:
+//   Scalar, Scalars, Args, ResultArgs   the types of its *_config.hpp
+//   row(m, P)                           scalars of one problem's state row at padded width P
+//   step(ctx, W, E, args, stream), results(result_args, stream)   the calls into its dispatch unit
+//   kPrefix                             what its refusals start with ("Lbfgs ask/tell", ...)
+//   kWhat                               how its HIP failures name the state ("ask/tell", "ask/tell f32")
+// and by its public handle struct H, which derives from Handle<T> and, where the defaults of Handle do not do, adds the
+// path's fields and its own kCounterWords, extra_bytes(), place_extras() and finish_args().
+#pragma once
+#include <memory>
+#include <new>
+#include <string>
+
+#include "engine_internal.hpp"
+
+namespace mi355 {
+namespace ask_tell_host {
+
+// One solve in flight: the state of all B problems in ONE device allocation,
+//   [ vectors B row | x_eval B n | scalars B | the path's extras | counters: active, then the path's ]
+// every part at a multiple of 16 bytes (carve()).
+template <class T>
+struct Handle {
+  using Traits = T;
+  using Scalar = typename T::Scalar;
+  mi355_lbfgs_ctx* ctx = nullptr;
+  char* block = nullptr;
+  size_t bytes = 0;
+  Scalar* x_eval = nullptr;
+  Scalar* vectors = nullptr;
+  typename T::Scalars* scalars = nullptr;
+  unsigned long long* active = nullptr;
+  int64_t B = 0;
+  int n = 0, m = 0, W = 0, E = 0;  // W lanes per problem at E coordinates per lane
+  mi355_lbfgs_stop stop = {};
+
+  // what a path without extras needs: the active counter alone, nothing between the scalars and the counters, and
+  // step arguments that are the common ones
+  static constexpr int kCounterWords = 1;
+  size_t extra_bytes() const { return 0; }
+  void place_extras(char*) {}
+  void finish_args(typename T::Args&) const {}
+};
+
+template <class T>
+int refuse(const char* text) {
+  return fail(MI355_ERR_UNSUPPORTED, std::string(T::kPrefix) + text);
+}
+
+// Everything checked before the device is touched, in the order the paths have always reported it: the refusals
+// (MI355_ERR_UNSUPPORTED, with the reason) — the shared ones here, the path's own in `before` and `after`, which stand
+// where they stood in the path's sequence — then validate()'s argument checks on the fields the path reads (the
+// objective and its parameters are not among them: the caller evaluates).
+template <class T, class Before, class After>
+int check_common(const mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, Before before, After after) {
+  if (!ctx) return fail(MI355_ERR_INVALID_ARGUMENT, "null context");
+  if (!desc) return fail(MI355_ERR_INVALID_ARGUMENT, "null desc");
+  if (desc->linesearch == MI355_LS_HAGER_ZHANG)
+    return refuse<T>(" is built with the More-Thuente line search only (no Hager-Zhang)");
+  int rc = before();
+  if (rc != MI355_OK) return rc;
+  if (desc->trace != nullptr) return refuse<T>(" records no per-iteration trace");
+  if (desc->per_problem_data != nullptr)
+    return refuse<T>(" takes no per_problem_data: the caller's evaluation holds the problem's data");
+  rc = after();
+  if (rc != MI355_OK) return rc;
+  mi355_lbfgs_desc read = *desc;  // the objective is the caller's: its id and parameter fields are not looked at
+  read.objective = MI355_OBJ_ROSENBROCK;
+  read.objective_params = nullptr;
+  read.n_params = 0;
+  read.per_problem_stride = 0;
+  return validate(ctx, &read, B);
+}
+
+// The two Lbfgs paths: their refusals around the shared ones (T::kRefusesLargeM: the float path words the m limit
+// itself, the double path leaves it to validate()), then the lane mapping — the caller's, or the narrowest built one
+// that covers n.
+template <class T>
+int check_lbfgs(const mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, int& W, int& E) {
+  const int rc = check_common<T>(
+      ctx, desc, B,
+      [&] {
+        if (desc->arithmetic == MI355_ARITH_FMA)
+          return refuse<T>(" is built for the exact arithmetic only (no MI355_ARITH_FMA)");
+        if (desc->history_placement == MI355_HISTORY_Y_IN_REGISTERS)
+          return refuse<T>(" keeps the history in device memory between calls (no MI355_HISTORY_Y_IN_REGISTERS)");
+        if (desc->hessian_from_functor) return refuse<T>(" is built for First-mode functions (no hessian_from_functor)");
+        if (desc->hessian_diagonal != nullptr) return refuse<T>(" is built for First-mode functions (no hessian_diagonal)");
+        if (desc->hessian_condition_stop > 0.0)
+          return refuse<T>(" is built for First-mode functions (no hessian_condition_stop)");
+        return static_cast<int>(MI355_OK);
+      },
+      [&] {
+        if (desc->n > MI355_LBFGS_MAX_N) return refuse<T>(" is built for n <= 256");
+        if (T::kRefusesLargeM && desc->m > MI355_LBFGS_MAX_M) return refuse<T>(" is built for m <= 32 (MI355_LBFGS_MAX_M)");
+        return static_cast<int>(MI355_OK);
+      });
+  if (rc != MI355_OK) return rc;
+  W = desc->lanes_per_problem;
+  E = desc->elems_per_lane;
+  if (W == 0 && E == 0) {
+    W = 8;
+    while (W < desc->n && W < 64) W <<= 1;
+  }
+  if (E == 0 && (W == 8 || W == 16 || W == 32 || W == 64)) E = (desc->n <= W) ? 1 : ((desc->n <= 2 * W) ? 2 : 4);
+  const bool built = ((W == 8 || W == 16 || W == 32 || W == 64) && E == 1) || (W == 64 && (E == 2 || E == 4));
+  if (!built || W * E < desc->n)
+    return refuse<T>(": this mapping is not built; it must cover n with 8, 16, 32 or 64 lanes at one coordinate per lane, "
+                     "or 64 lanes at two or four");
+  return MI355_OK;
+}
+
+// The one layout of the three handles: byte offsets of the parts after the vectors (which start the block), each a
+// multiple of 16, and the size of the whole.
+struct Layout {
+  size_t x_eval, scalars, extras, counters, bytes;
+};
+
+template <class H>
+Layout carve(const H& h, size_t row) {
+  using T = typename H::Traits;
+  const auto round16 = [](size_t bytes) { return (bytes + 15) & ~static_cast<size_t>(15); };
+  const size_t B = static_cast<size_t>(h.B);
+  Layout l;
+  l.x_eval = round16(B * row * sizeof(typename T::Scalar));
+  l.scalars = l.x_eval + round16(B * h.n * sizeof(typename T::Scalar));
+  l.extras = l.scalars + round16(B * sizeof(typename T::Scalars));
+  l.counters = l.extras + round16(h.extra_bytes());
+  l.bytes = l.counters + H::kCounterWords * sizeof(unsigned long long);
+  return l;
+}
+
+template <class H>
+typename H::Traits::Args step_args(const H* h, const typename H::Scalar* f, const typename H::Scalar* g) {
+  typename H::Traits::Args a;
+  a.vectors = h->vectors;
+  a.scalars = h->scalars;
+  a.x_eval = h->x_eval;
+  a.f = f;
+  a.g = g;
+  a.active = h->active;
+  a.B = h->B;
+  a.n = h->n;
+  a.m = h->m;
+  a.stop = h->stop;
+  h->finish_args(a);
+  return a;
+}
+
+// check(H&): the path's checks; on MI355_OK it has set the path's mapping fields (and n-dependent extras) in the handle
+// it was given.  init(H&, row, stream): the path's state initialisation launch, run when B > 0.
+template <class H, class Check, class Init>
+int create(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const typename H::Scalar* x0, void* stream_,
+           H** out, Check check, Init init) {
+  using T = typename H::Traits;
+  if (!out) return fail(MI355_ERR_INVALID_ARGUMENT, "null handle pointer");
+  *out = nullptr;
+  H checked;
+  const int rc = check(checked);
+  if (rc != MI355_OK) return rc;
+  if (B > 0 && !x0) return fail(MI355_ERR_INVALID_ARGUMENT, "null x0");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MI355_ENTER_DEVICE(ctx);
+  const std::string what = T::kWhat;
+  std::unique_ptr<H> h(new (std::nothrow) H(checked));
+  if (!h) return fail(MI355_ERR_HIP, what + " handle allocation failed");
+  h->ctx = ctx;
+  h->B = B;
+  h->n = desc->n;
+  h->m = desc->m;
+  h->stop = desc->stop;
+  const size_t row = static_cast<size_t>(T::row(h->m, h->W * h->E));
+  const Layout at = carve(*h, row);
+  h->bytes = at.bytes;
+  const hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->block), h->bytes);
+  if (e != hipSuccess)
+    return fail(MI355_ERR_HIP, "hipMalloc of the " + what + " state (" + std::to_string(at.bytes) + " bytes): " + hipGetErrorString(e));
+  h->vectors = reinterpret_cast<typename H::Scalar*>(h->block);
+  h->x_eval = reinterpret_cast<typename H::Scalar*>(h->block + at.x_eval);
+  h->scalars = reinterpret_cast<typename T::Scalars*>(h->block + at.scalars);
+  h->active = reinterpret_cast<unsigned long long*>(h->block + at.counters);
+  h->place_extras(h->block + at.extras);
+  // everything zero: padding, histories and scalars (phase: first evaluation pending), the path's extras and counters;
+  // then every problem counts as active
+  hipError_t he = hipMemsetAsync(h->block, 0, h->bytes, stream);
+  if (he == hipSuccess) {
+    const unsigned long long all = static_cast<unsigned long long>(B);
+    he = hipMemcpyAsync(h->active, &all, sizeof(all), hipMemcpyHostToDevice, stream);
+  }
+  int status = MI355_OK;
+  if (he != hipSuccess) status = fail(MI355_ERR_HIP, what + " state initialisation: " + hipGetErrorString(he));
+  if (status == MI355_OK && B > 0) status = init(*h, static_cast<long long>(row), stream);
+  if (status != MI355_OK) {
+    (void)hipFree(h->block);
+    return status;
+  }
+  *out = h.release();
+  return MI355_OK;
+}
+
+template <class H>
+int x(H* handle, const typename H::Scalar** x_eval) {
+  if (!handle || !x_eval) return fail(MI355_ERR_INVALID_ARGUMENT, "null argument");
+  *x_eval = handle->x_eval;
+  return MI355_OK;
+}
+
+template <class H>
+int step(H* handle, const typename H::Scalar* f, const typename H::Scalar* g, int64_t* active_host, void* stream_) {
+  if (!handle) return fail(MI355_ERR_INVALID_ARGUMENT, "null handle");
+  if (handle->B > 0 && (!f || !g)) return fail(MI355_ERR_INVALID_ARGUMENT, "null f / g");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MI355_ENTER_DEVICE(handle->ctx);
+  if (handle->B > 0) {
+    const int rc = H::Traits::step(handle->ctx, handle->W, handle->E, step_args(handle, f, g), stream);
+    if (rc != MI355_OK) return rc;
+  }
+  if (active_host) {
+    unsigned long long count = 0;
+    HIP_TRY(hipMemcpyAsync(&count, handle->active, sizeof(count), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *active_host = static_cast<int64_t>(count);
+  }
+  return MI355_OK;
+}
+
+template <class H>
+int active(H* handle, const int64_t** active_dev) {
+  if (!handle || !active_dev) return fail(MI355_ERR_INVALID_ARGUMENT, "null argument");
+  *active_dev = reinterpret_cast<const int64_t*>(handle->active);
+  return MI355_OK;
+}
+
+template <class H>
+int results(H* handle, typename H::Scalar* x_out, typename H::Scalar* f_out, typename H::Scalar* g_out,
+            mi355_lbfgs_progress* progress_out, void* stream_) {
+  using T = typename H::Traits;
+  if (!handle) return fail(MI355_ERR_INVALID_ARGUMENT, "null handle");
+  if (handle->B == 0) return MI355_OK;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MI355_ENTER_DEVICE(handle->ctx);
+  typename T::ResultArgs r;
+  r.vectors = handle->vectors;
+  r.scalars = handle->scalars;
+  r.x_out = x_out;
+  r.f_out = f_out;
+  r.g_out = g_out;
+  r.progress_out = progress_out;
+  r.B = handle->B;
+  r.row_p = static_cast<long long>(handle->W) * handle->E;
+  r.row = T::row(handle->m, handle->W * handle->E);
+  r.n = handle->n;
+  return T::results(r, stream);
+}
+
+template <class H>
+int destroy(H* handle) {
+  if (!handle) return MI355_OK;
+  MI355_ENTER_DEVICE(handle->ctx);
+  const hipError_t e = hipFree(handle->block);  // (waits for the device: no kernel still reads the state)
+  delete handle;
+  if (e != hipSuccess)
+    return fail(MI355_ERR_HIP, std::string("hipFree of the ") + H::Traits::kWhat + " state: " + hipGetErrorString(e));
+  return MI355_OK;
+}
+
+}  // namespace ask_tell_host
+
+// The step launch of the three dispatch units.  kern: a __global__ function taking the path's Args, one wavefront per
+// workgroup, W lanes per problem at E coordinates per lane; dynamic_lds: its dynamic LDS bytes (0: none, and the
+// kernel's limit is left alone); reported_lds: what last_launch() says (the static LDS of a kernel without dynamic).
+// A grid-stride loop over the batch: as many workgroups as the chip holds (or the batch needs).
+template <int W, int E, class Kernel, class Args>
+int launch_ask_tell_step(mi355_lbfgs_ctx* ctx, Kernel kern, int dynamic_lds, int reported_lds, const Args& args,
+                         hipStream_t stream) {
+  constexpr int kSegs = kWave / W;
+  if (args.n > W * E) return fail(MI355_ERR_INVALID_ARGUMENT, "internal: the lane mapping does not cover n");
+  if (dynamic_lds > 0)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, dynamic_lds));
+  int per_cu = 0;
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kWave, dynamic_lds));
+  if (per_cu < 1) per_cu = 1;
+  const long long blocks_needed = (args.B + kSegs - 1) / kSegs;
+  long long blocks_ll = static_cast<long long>(per_cu) * ctx->num_cus;
+  if (ctx->debug_blocks >= 1 && ctx->debug_blocks < blocks_ll) blocks_ll = ctx->debug_blocks;
+  if (blocks_ll > blocks_needed) blocks_ll = blocks_needed;
+  HIP_TRY(hipMemsetAsync(args.active, 0, sizeof(unsigned long long), stream));
+  HIP_TRY(hipEventRecord(ctx->ev_start, stream));
+  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks_ll)), dim3(kWave), dynamic_lds, stream, args);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ctx->ev_stop, stream));
+  ctx->timed = true;
+  ctx->last_W = W;
+  ctx->last_E = E;
+  ctx->last_blocks = static_cast<int>(blocks_ll);
+  ctx->last_threads = kWave;
+  ctx->last_lds = reported_lds;
+  ctx->last_mr = 0;
+  ctx->last_variant = MI355_KERNEL_GENERAL;
+  ctx->last_arith = MI355_ARITH_EXACT;
+  return MI355_OK;
+}
+
+// kern(args...) with one thread per element, `total` = B n of them: the state initialisations and the result gathers
+template <class Kernel, class... A>
+int launch_elementwise(Kernel kern, long long total, hipStream_t stream, const A&... args) {
+  const long long blocks = (total + 255) / 256;
+  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, args...);
+  HIP_TRY(hipGetLastError());
+  return MI355_OK;
+}
+
+}  // namespace mi355

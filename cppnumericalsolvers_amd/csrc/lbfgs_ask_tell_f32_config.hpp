@@ -1,6 +1,6 @@
 // lbfgs_ask_tell_f32_config.hpp — what the entry points, the dispatch unit and the kernel of the float ask/tell (reverse
 // communication) L-BFGS path share (lbfgs_ask_tell_f32_kernel.hpp, dispatch_lbfgs_ask_tell_f32.hip,
-// ask_tell_f32_entry.hip).  The phase words are those of lbfgs_ask_tell_config.hpp.
+// ask_tell_entry.hip).  The phase words are those of lbfgs_ask_tell_config.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

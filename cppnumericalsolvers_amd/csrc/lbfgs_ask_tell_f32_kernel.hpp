@@ -12,7 +12,7 @@
 //     ||x||_inf;
 //   * every constant is static_cast<float>(double literal); the thresholds of the stop record arrive converted once;
 //   * the three doubles of the progress record are the float values widened, a NaN among the results is the canonical
-//     quiet NaN (results_kernel);
+//     quiet NaN (CanonicalNan, applied by the shared result gather);
 //   * exact arithmetic only (the unit is built with -ffp-contract=off).
 //
 // Mapping: one problem per segment of W lanes, lane sl owns coordinates sl * E + e; every reduction is a segment
@@ -31,6 +31,7 @@
 #include "lbfgs_f32_kernel.hpp"
 #include "more_thuente_f32_device.hpp"
 #include "wave_primitives_f32.hpp"
+#include "ask_tell_kernel_common.hpp"
 
 namespace mi355 {
 namespace ask_tell_f32 {
@@ -464,46 +465,13 @@ __global__ __launch_bounds__(64) void step_kernel(const Args a) {
   if (lane == 0 && active_count != 0) atomicAdd(a.active, active_count);
 }
 
-// x0 into the evaluation buffer and into the state row (whose padding and scalars the host has zeroed: phase
-// "first evaluation pending"), so that results() before the first step returns the start point
-__global__ void init_kernel(float* vectors, Scalars* scalars, float* x_eval, const float* x0, long long B, int n,
-                            long long row) {
-  const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t >= B * n) return;
-  const long long b = t / n;
-  const int j = static_cast<int>(t - b * n);
-  const float v = x0[t];
-  x_eval[t] = v;
-  vectors[b * row + j] = v;
-  if (j == 0) scalars[b].status = MI355_STATUS_NOT_STARTED;
-}
-
-// x, f, g and the progress record as the persistent float kernel returns them: the three doubles are the float values
-// widened, every NaN is the canonical quiet NaN
-__global__ void results_kernel(const ResultArgs r) {
-  const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t >= r.B * r.n) return;
-  const long long b = t / r.n;
-  const int j = static_cast<int>(t - b * r.n);
-  const float* const vec = r.vectors + b * r.row;
-  if (r.x_out) r.x_out[t] = f32::canonical_nan(vec[j]);
-  if (r.g_out) r.g_out[t] = f32::canonical_nan(vec[r.row_p + j]);
-  if (j == 0) {
-    const Scalars& s = r.scalars[b];
-    if (r.f_out) r.f_out[b] = f32::canonical_nan(s.f);
-    if (r.progress_out) {
-      mi355_lbfgs_progress pr;
-      pr.status = s.status;
-      pr.num_iterations = s.num_iterations;
-      pr.nfev = s.nfev;
-      pr.sum_k = s.sum_k;
-      pr.x_delta = f32::canonical_nan_widened(s.x_delta);
-      pr.f_delta = f32::canonical_nan_widened(s.f_delta);
-      pr.gradient_norm = f32::canonical_nan_widened(s.gradient_norm);
-      r.progress_out[b] = pr;
-    }
-  }
-}
+// How the result gather (ask_tell_kernel_common.hpp) finishes a value, as the persistent float kernel returns them: the
+// three doubles of the progress record are the float values widened, every NaN is the canonical quiet NaN.  (The state
+// initialisation is ask_tell_kernel_common.hpp's too.)
+struct CanonicalNan {
+  __device__ static float value(float v) { return f32::canonical_nan(v); }
+  __device__ static double widened(float v) { return f32::canonical_nan_widened(v); }
+};
 
 }  // namespace ask_tell_f32
 }  // namespace mi355

@@ -27,6 +27,7 @@
 #include "more_thuente_device.hpp"
 #include "progress_device.hpp"
 #include "wave_primitives.hpp"
+#include "ask_tell_kernel_common.hpp"
 
 namespace mi355 {
 namespace ask_tell {
@@ -422,44 +423,7 @@ __global__ __launch_bounds__(64) void step_kernel(const Args a) {
   if (lane == 0 && active_count != 0) atomicAdd(a.active, active_count);
 }
 
-// x0 into the evaluation buffer and into the state row (whose padding and scalars the host has zeroed: phase
-// "first evaluation pending"), so that results() before the first step returns the start point
-__global__ void init_kernel(double* vectors, Scalars* scalars, double* x_eval, const double* x0, long long B, int n,
-                            long long row) {
-  const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t >= B * n) return;
-  const long long b = t / n;
-  const int j = static_cast<int>(t - b * n);
-  const double v = x0[t];
-  x_eval[t] = v;
-  vectors[b * row + j] = v;
-  if (j == 0) scalars[b].status = MI355_STATUS_NOT_STARTED;
-}
-
-__global__ void results_kernel(const ResultArgs r) {
-  const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t >= r.B * r.n) return;
-  const long long b = t / r.n;
-  const int j = static_cast<int>(t - b * r.n);
-  const double* const vec = r.vectors + b * r.row;
-  if (r.x_out) r.x_out[t] = vec[j];
-  if (r.g_out) r.g_out[t] = vec[r.row_p + j];
-  if (j == 0) {
-    const Scalars& s = r.scalars[b];
-    if (r.f_out) r.f_out[b] = s.f;
-    if (r.progress_out) {
-      mi355_lbfgs_progress pr;
-      pr.status = s.status;
-      pr.num_iterations = s.num_iterations;
-      pr.nfev = s.nfev;
-      pr.sum_k = s.sum_k;
-      pr.x_delta = s.x_delta;
-      pr.f_delta = s.f_delta;
-      pr.gradient_norm = s.gradient_norm;
-      r.progress_out[b] = pr;
-    }
-  }
-}
+// (the state initialisation and the result gather are ask_tell_kernel_common.hpp's)
 
 }  // namespace ask_tell
 }  // namespace mi355

@@ -1,5 +1,5 @@
 // lbfgsb_ask_tell_config.hpp — what the entry points, the dispatch unit and the kernel of the ask/tell (reverse
-// communication) L-BFGS-B path share (lbfgsb_ask_tell_kernel.hpp, dispatch_lbfgsb_ask_tell.hip, lbfgsb_ask_tell_entry.hip).
+// communication) L-BFGS-B path share (lbfgsb_ask_tell_kernel.hpp, dispatch_lbfgsb_ask_tell.hip, ask_tell_entry.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -28,6 +28,7 @@
 #pragma once
 #include "lbfgsb_ask_tell_config.hpp"
 #include "lbfgsb_kernel.hpp"
+#include "ask_tell_kernel_common.hpp"
 
 namespace mi355 {
 namespace ask_tell_box {
@@ -989,30 +990,7 @@ __global__ void init_kernel(const InitArgs a) {
   }
 }
 
-__global__ void results_kernel(const ResultArgs r) {
-  const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t >= r.B * r.n) return;
-  const long long b = t / r.n;
-  const int j = static_cast<int>(t - b * r.n);
-  const double* const vec = r.vectors + b * r.row;
-  if (r.x_out) r.x_out[t] = vec[j];
-  if (r.g_out) r.g_out[t] = vec[r.row_p + j];
-  if (j == 0) {
-    const Scalars& s = r.scalars[b];
-    if (r.f_out) r.f_out[b] = s.f;
-    if (r.progress_out) {
-      mi355_lbfgs_progress pr;
-      pr.status = s.status;
-      pr.num_iterations = s.num_iterations;
-      pr.nfev = s.nfev;
-      pr.sum_k = s.sum_k;
-      pr.x_delta = s.x_delta;
-      pr.f_delta = s.f_delta;
-      pr.gradient_norm = s.gradient_norm;
-      r.progress_out[b] = pr;
-    }
-  }
-}
+// (the result gather is ask_tell_kernel_common.hpp's)
 
 }  // namespace ask_tell_box
 }  // namespace mi355

@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <utility>
 
 #include "context.h"
@@ -46,120 +47,128 @@ inline mi355_lbfgs_desc AskTellDesc(int n, int m = 10, const mi355_lbfgs_stop* s
   return d;
 }
 
-class LbfgsAskTell {
- public:
+namespace detail {
+
+// What tells the three C handle types apart: the scalar, the handle, its C functions, and the names a failure reports
+// (the class for a null context, "<kPrefix><function>" for a C call).
+struct LbfgsAskTellApi {
   using Scalar = double;
-  // x0_dev: DEVICE [B][n].  stream: a hipStream_t (nullptr: the default stream) for this and every later call.
-  LbfgsAskTell(std::shared_ptr<Context> context, const mi355_lbfgs_desc& desc, int64_t B, const double* x0_dev,
-               void* stream = nullptr)
-      : context_(std::move(context)), stream_(stream), B_(B), n_(desc.n) {
-    if (!context_) Fail("LbfgsAskTell: null context");
-    Check(mi355_lbfgs_ask_tell_create(context_->get(), &desc, B, x0_dev, stream_, &handle_), "mi355_lbfgs_ask_tell_create");
-    Check(mi355_lbfgs_ask_tell_x(handle_, &x_), "mi355_lbfgs_ask_tell_x");
-  }
-  ~LbfgsAskTell() { (void)mi355_lbfgs_ask_tell_destroy(handle_); }
-  LbfgsAskTell(const LbfgsAskTell&) = delete;
-  LbfgsAskTell& operator=(const LbfgsAskTell&) = delete;
-  LbfgsAskTell(LbfgsAskTell&& other) noexcept
+  using Handle = mi355_lbfgs_ask_tell;
+  static constexpr auto create = &mi355_lbfgs_ask_tell_create;
+  static constexpr auto x = &mi355_lbfgs_ask_tell_x;
+  static constexpr auto step = &mi355_lbfgs_ask_tell_step;
+  static constexpr auto active = &mi355_lbfgs_ask_tell_active;
+  static constexpr auto results = &mi355_lbfgs_ask_tell_results;
+  static constexpr auto destroy = &mi355_lbfgs_ask_tell_destroy;
+  static constexpr const char* kClass = "LbfgsAskTell";
+  static constexpr const char* kPrefix = "mi355_lbfgs_ask_tell_";
+};
+struct LbfgsAskTellF32Api {
+  using Scalar = float;
+  using Handle = mi355_lbfgs_ask_tell_f32;
+  static constexpr auto create = &mi355_lbfgs_ask_tell_f32_create;
+  static constexpr auto x = &mi355_lbfgs_ask_tell_f32_x;
+  static constexpr auto step = &mi355_lbfgs_ask_tell_f32_step;
+  static constexpr auto active = &mi355_lbfgs_ask_tell_f32_active;
+  static constexpr auto results = &mi355_lbfgs_ask_tell_f32_results;
+  static constexpr auto destroy = &mi355_lbfgs_ask_tell_f32_destroy;
+  static constexpr const char* kClass = "LbfgsAskTellF32";
+  static constexpr const char* kPrefix = "mi355_lbfgs_ask_tell_f32_";
+};
+struct LbfgsbAskTellApi {
+  using Scalar = double;
+  using Handle = mi355_lbfgsb_ask_tell;
+  static constexpr auto create = &mi355_lbfgsb_ask_tell_create;
+  static constexpr auto x = &mi355_lbfgsb_ask_tell_x;
+  static constexpr auto step = &mi355_lbfgsb_ask_tell_step;
+  static constexpr auto active = &mi355_lbfgsb_ask_tell_active;
+  static constexpr auto results = &mi355_lbfgsb_ask_tell_results;
+  static constexpr auto destroy = &mi355_lbfgsb_ask_tell_destroy;
+  static constexpr const char* kClass = "LbfgsbAskTell";
+  static constexpr const char* kPrefix = "mi355_lbfgsb_ask_tell_";
+};
+
+// The RAII handle of one batched solve over the C handle of `Api`: what LbfgsAskTell, LbfgsAskTellF32 and LbfgsbAskTell are.
+template <class Api>
+class AskTellHandle {
+ public:
+  using Scalar = typename Api::Scalar;
+  // x0_dev: DEVICE [B][n] of Scalar.  stream: a hipStream_t (nullptr: the default stream) for this and every later call.
+  AskTellHandle(std::shared_ptr<Context> context, const mi355_lbfgs_desc& desc, int64_t B, const Scalar* x0_dev,
+                void* stream = nullptr)
+      : AskTellHandle(std::move(context), desc.n, B, stream, [&](mi355_lbfgs_ctx* ctx, typename Api::Handle** out) {
+          return Api::create(ctx, &desc, B, x0_dev, stream, out);
+        }) {}
+  ~AskTellHandle() { (void)Api::destroy(handle_); }
+  AskTellHandle(const AskTellHandle&) = delete;
+  AskTellHandle& operator=(const AskTellHandle&) = delete;
+  AskTellHandle(AskTellHandle&& other) noexcept
       : context_(std::move(other.context_)), handle_(other.handle_), x_(other.x_), stream_(other.stream_), B_(other.B_),
         n_(other.n_) {
     other.handle_ = nullptr;
   }
-  LbfgsAskTell& operator=(LbfgsAskTell&&) = delete;
+  AskTellHandle& operator=(AskTellHandle&&) = delete;
 
   // DEVICE [B][n]: the points to evaluate (rows of finished problems hold their returned x)
-  const double* Ask() const { return x_; }
+  const Scalar* Ask() const { return x_; }
   // f_dev [B], g_dev [B][n]: the evaluation of Ask()'s rows.  Waits for the stream; returns the problems still active.
-  int64_t Tell(const double* f_dev, const double* g_dev) {
+  int64_t Tell(const Scalar* f_dev, const Scalar* g_dev) {
     int64_t active = 0;
-    Check(mi355_lbfgs_ask_tell_step(handle_, f_dev, g_dev, &active, stream_), "mi355_lbfgs_ask_tell_step");
+    Checked(Api::step(handle_, f_dev, g_dev, &active, stream_), "step");
     return active;
   }
   // ... without waiting: the count is behind ActiveDevice() once the stream has run the call
-  void TellAsync(const double* f_dev, const double* g_dev) {
-    Check(mi355_lbfgs_ask_tell_step(handle_, f_dev, g_dev, nullptr, stream_), "mi355_lbfgs_ask_tell_step");
+  void TellAsync(const Scalar* f_dev, const Scalar* g_dev) {
+    Checked(Api::step(handle_, f_dev, g_dev, nullptr, stream_), "step");
   }
   const int64_t* ActiveDevice() const {
     const int64_t* p = nullptr;
-    Check(mi355_lbfgs_ask_tell_active(handle_, &p), "mi355_lbfgs_ask_tell_active");
+    Checked(Api::active(handle_, &p), "active");
     return p;
   }
   // The current iterate of every problem, its value, gradient and progress record into DEVICE arrays (any may be null);
   // asynchronous on the stream.
-  void Results(double* x_dev, double* f_dev, double* g_dev, mi355_lbfgs_progress* progress_dev) const {
-    Check(mi355_lbfgs_ask_tell_results(handle_, x_dev, f_dev, g_dev, progress_dev, stream_), "mi355_lbfgs_ask_tell_results");
+  void Results(Scalar* x_dev, Scalar* f_dev, Scalar* g_dev, mi355_lbfgs_progress* progress_dev) const {
+    Checked(Api::results(handle_, x_dev, f_dev, g_dev, progress_dev, stream_), "results");
   }
   int64_t batch() const { return B_; }
   int dimension() const { return n_; }
   void* stream() const { return stream_; }
 
- private:
+ protected:
+  // create(ctx, &handle): the path's C create call, for a path whose create takes more than the common arguments
+  template <class Create>
+  AskTellHandle(std::shared_ptr<Context> context, int n, int64_t B, void* stream, Create create)
+      : context_(std::move(context)), stream_(stream), B_(B), n_(n) {
+    if (!context_) Fail(std::string(Api::kClass) + ": null context");
+    Checked(create(context_->get(), &handle_), "create");
+    Checked(Api::x(handle_, &x_), "x");
+  }
+  // Check() under the C function's full name, put together only when the call failed
+  static void Checked(int rc, const char* function) {
+    if (rc != MI355_OK) Check(rc, (std::string(Api::kPrefix) + function).c_str());
+  }
+
   std::shared_ptr<Context> context_;
-  mi355_lbfgs_ask_tell* handle_ = nullptr;
-  const double* x_ = nullptr;
+  typename Api::Handle* handle_ = nullptr;
+  const Scalar* x_ = nullptr;
   void* stream_ = nullptr;
   int64_t B_ = 0;
   int n_ = 0;
 };
 
+}  // namespace detail
+
+class LbfgsAskTell : public detail::AskTellHandle<detail::LbfgsAskTellApi> {
+ public:
+  using AskTellHandle::AskTellHandle;
+};
+
 // ---- Lbfgs<F, m, MoreThuente> with ScalarType = float in the same form (mi355_lbfgs_ask_tell_f32_*) -----------------
 // Every device array is float; the desc is AskTellDesc's (its thresholds are converted to float once by the library).
-class LbfgsAskTellF32 {
+class LbfgsAskTellF32 : public detail::AskTellHandle<detail::LbfgsAskTellF32Api> {
  public:
-  using Scalar = float;
-  // x0_dev: DEVICE [B][n] floats.  stream: a hipStream_t (nullptr: the default stream) for this and every later call.
-  LbfgsAskTellF32(std::shared_ptr<Context> context, const mi355_lbfgs_desc& desc, int64_t B, const float* x0_dev,
-                  void* stream = nullptr)
-      : context_(std::move(context)), stream_(stream), B_(B), n_(desc.n) {
-    if (!context_) Fail("LbfgsAskTellF32: null context");
-    Check(mi355_lbfgs_ask_tell_f32_create(context_->get(), &desc, B, x0_dev, stream_, &handle_),
-          "mi355_lbfgs_ask_tell_f32_create");
-    Check(mi355_lbfgs_ask_tell_f32_x(handle_, &x_), "mi355_lbfgs_ask_tell_f32_x");
-  }
-  ~LbfgsAskTellF32() { (void)mi355_lbfgs_ask_tell_f32_destroy(handle_); }
-  LbfgsAskTellF32(const LbfgsAskTellF32&) = delete;
-  LbfgsAskTellF32& operator=(const LbfgsAskTellF32&) = delete;
-  LbfgsAskTellF32(LbfgsAskTellF32&& other) noexcept
-      : context_(std::move(other.context_)), handle_(other.handle_), x_(other.x_), stream_(other.stream_), B_(other.B_),
-        n_(other.n_) {
-    other.handle_ = nullptr;
-  }
-  LbfgsAskTellF32& operator=(LbfgsAskTellF32&&) = delete;
-
-  // DEVICE [B][n]: the points to evaluate (rows of finished problems hold their returned x)
-  const float* Ask() const { return x_; }
-  // f_dev [B], g_dev [B][n]: the evaluation of Ask()'s rows.  Waits for the stream; returns the problems still active.
-  int64_t Tell(const float* f_dev, const float* g_dev) {
-    int64_t active = 0;
-    Check(mi355_lbfgs_ask_tell_f32_step(handle_, f_dev, g_dev, &active, stream_), "mi355_lbfgs_ask_tell_f32_step");
-    return active;
-  }
-  // ... without waiting: the count is behind ActiveDevice() once the stream has run the call
-  void TellAsync(const float* f_dev, const float* g_dev) {
-    Check(mi355_lbfgs_ask_tell_f32_step(handle_, f_dev, g_dev, nullptr, stream_), "mi355_lbfgs_ask_tell_f32_step");
-  }
-  const int64_t* ActiveDevice() const {
-    const int64_t* p = nullptr;
-    Check(mi355_lbfgs_ask_tell_f32_active(handle_, &p), "mi355_lbfgs_ask_tell_f32_active");
-    return p;
-  }
-  // The current iterate of every problem, its value, gradient and progress record into DEVICE arrays (any may be null);
-  // asynchronous on the stream.
-  void Results(float* x_dev, float* f_dev, float* g_dev, mi355_lbfgs_progress* progress_dev) const {
-    Check(mi355_lbfgs_ask_tell_f32_results(handle_, x_dev, f_dev, g_dev, progress_dev, stream_),
-          "mi355_lbfgs_ask_tell_f32_results");
-  }
-  int64_t batch() const { return B_; }
-  int dimension() const { return n_; }
-  void* stream() const { return stream_; }
-
- private:
-  std::shared_ptr<Context> context_;
-  mi355_lbfgs_ask_tell_f32* handle_ = nullptr;
-  const float* x_ = nullptr;
-  void* stream_ = nullptr;
-  int64_t B_ = 0;
-  int n_ = 0;
+  using AskTellHandle::AskTellHandle;
 };
 
 // ---- Lbfgsb<F, m, MoreThuente> in the same form (mi355_lbfgsb_ask_tell_*): simple bounds on the parameters -------------
@@ -186,9 +195,8 @@ struct LbfgsbAsks {
   int64_t clip_start = 0, trial = 0, cauchy = 0, clip_next = 0, first = 0;
 };
 
-class LbfgsbAskTell {
+class LbfgsbAskTell : public detail::AskTellHandle<detail::LbfgsbAskTellApi> {
  public:
-  using Scalar = double;
   // No box: the reference's default unbounded one.  x0_dev: DEVICE [B][n]; stream as for LbfgsAskTell.
   LbfgsbAskTell(std::shared_ptr<Context> context, const mi355_lbfgs_desc& desc, int64_t B, const double* x0_dev,
                 void* stream = nullptr)
@@ -200,43 +208,14 @@ class LbfgsbAskTell {
   // One box per problem: DEVICE rows of box_stride >= n doubles.  The handle copies the box: the caller's may go.
   LbfgsbAskTell(std::shared_ptr<Context> context, const mi355_lbfgs_desc& desc, const double* lower_dev,
                 const double* upper_dev, int64_t box_stride, int64_t B, const double* x0_dev, void* stream = nullptr)
-      : context_(std::move(context)), stream_(stream), B_(B), n_(desc.n) {
-    if (!context_) Fail("LbfgsbAskTell: null context");
-    Check(mi355_lbfgsb_ask_tell_create(context_->get(), &desc, lower_dev, upper_dev, box_stride, B, x0_dev, stream_, &handle_),
-          "mi355_lbfgsb_ask_tell_create");
-    Check(mi355_lbfgsb_ask_tell_x(handle_, &x_), "mi355_lbfgsb_ask_tell_x");
-  }
-  ~LbfgsbAskTell() { (void)mi355_lbfgsb_ask_tell_destroy(handle_); }
-  LbfgsbAskTell(const LbfgsbAskTell&) = delete;
-  LbfgsbAskTell& operator=(const LbfgsbAskTell&) = delete;
-  LbfgsbAskTell(LbfgsbAskTell&& other) noexcept
-      : context_(std::move(other.context_)), handle_(other.handle_), x_(other.x_), stream_(other.stream_), B_(other.B_),
-        n_(other.n_) {
-    other.handle_ = nullptr;
-  }
-  LbfgsbAskTell& operator=(LbfgsbAskTell&&) = delete;
+      : AskTellHandle(std::move(context), desc.n, B, stream, [&](mi355_lbfgs_ctx* ctx, mi355_lbfgsb_ask_tell** out) {
+          return mi355_lbfgsb_ask_tell_create(ctx, &desc, lower_dev, upper_dev, box_stride, B, x0_dev, stream, out);
+        }) {}
 
-  const double* Ask() const { return x_; }
-  int64_t Tell(const double* f_dev, const double* g_dev) {
-    int64_t active = 0;
-    Check(mi355_lbfgsb_ask_tell_step(handle_, f_dev, g_dev, &active, stream_), "mi355_lbfgsb_ask_tell_step");
-    return active;
-  }
-  void TellAsync(const double* f_dev, const double* g_dev) {
-    Check(mi355_lbfgsb_ask_tell_step(handle_, f_dev, g_dev, nullptr, stream_), "mi355_lbfgsb_ask_tell_step");
-  }
-  const int64_t* ActiveDevice() const {
-    const int64_t* p = nullptr;
-    Check(mi355_lbfgsb_ask_tell_active(handle_, &p), "mi355_lbfgsb_ask_tell_active");
-    return p;
-  }
-  void Results(double* x_dev, double* f_dev, double* g_dev, mi355_lbfgs_progress* progress_dev) const {
-    Check(mi355_lbfgsb_ask_tell_results(handle_, x_dev, f_dev, g_dev, progress_dev, stream_), "mi355_lbfgsb_ask_tell_results");
-  }
   // waits for the stream
   LbfgsbAsks Asks() const {
     int64_t c[5] = {0, 0, 0, 0, 0};
-    Check(mi355_lbfgsb_ask_tell_asks(handle_, c, stream_), "mi355_lbfgsb_ask_tell_asks");
+    Checked(mi355_lbfgsb_ask_tell_asks(handle_, c, stream_), "asks");
     LbfgsbAsks a;
     a.clip_start = c[0];
     a.trial = c[1];
@@ -245,17 +224,6 @@ class LbfgsbAskTell {
     a.first = c[4];
     return a;
   }
-  int64_t batch() const { return B_; }
-  int dimension() const { return n_; }
-  void* stream() const { return stream_; }
-
- private:
-  std::shared_ptr<Context> context_;
-  mi355_lbfgsb_ask_tell* handle_ = nullptr;
-  const double* x_ = nullptr;
-  void* stream_ = nullptr;
-  int64_t B_ = 0;
-  int n_ = 0;
 };
 
 // The loop: evaluate, tell, until no problem is active.  f_dev [B] and g_dev [B][n] are the caller's work arrays; the
@@ -278,28 +246,18 @@ int64_t MinimizeBatchWith(Evaluator&& evaluator, Handle& solve, typename Handle:
   }
 }
 
-// ... from the start points to the results, all DEVICE arrays (g_out / progress_out may be null)
-template <class Evaluator>
+// ... from the start points to the results, all DEVICE arrays (g_out / progress_out may be null).  x0_dev decides the
+// precision: double arrays run LbfgsAskTell, float arrays LbfgsAskTellF32.
+template <class Evaluator, class Scalar,
+          class Solve = std::conditional_t<std::is_same<Scalar, float>::value, LbfgsAskTellF32, LbfgsAskTell>>
 int64_t MinimizeBatchWith(Evaluator&& evaluator, std::shared_ptr<Context> context, const mi355_lbfgs_desc& desc, int64_t B,
-                          const double* x0_dev, double* f_work_dev, double* g_work_dev, double* x_out, double* f_out,
-                          double* g_out, mi355_lbfgs_progress* progress_out, void* stream = nullptr,
-                          int64_t max_rounds = -1) {
-  LbfgsAskTell solve(std::move(context), desc, B, x0_dev, stream);
+                          const Scalar* x0_dev, typename Solve::Scalar* f_work_dev, typename Solve::Scalar* g_work_dev,
+                          typename Solve::Scalar* x_out, typename Solve::Scalar* f_out, typename Solve::Scalar* g_out,
+                          mi355_lbfgs_progress* progress_out, void* stream = nullptr, int64_t max_rounds = -1) {
+  Solve solve(std::move(context), desc, B, x0_dev, stream);
   const int64_t rounds = MinimizeBatchWith(std::forward<Evaluator>(evaluator), solve, f_work_dev, g_work_dev, max_rounds);
   solve.Results(x_out, f_out, g_out, progress_out);
   return rounds;   // (the handle's destructor waits for the device: the results are in place)
-}
-
-// ... the same in native float (LbfgsAskTellF32)
-template <class Evaluator>
-int64_t MinimizeBatchWith(Evaluator&& evaluator, std::shared_ptr<Context> context, const mi355_lbfgs_desc& desc, int64_t B,
-                          const float* x0_dev, float* f_work_dev, float* g_work_dev, float* x_out, float* f_out,
-                          float* g_out, mi355_lbfgs_progress* progress_out, void* stream = nullptr,
-                          int64_t max_rounds = -1) {
-  LbfgsAskTellF32 solve(std::move(context), desc, B, x0_dev, stream);
-  const int64_t rounds = MinimizeBatchWith(std::forward<Evaluator>(evaluator), solve, f_work_dev, g_work_dev, max_rounds);
-  solve.Results(x_out, f_out, g_out, progress_out);
-  return rounds;
 }
 
 }  // namespace cppoptlib::mi355
