@@ -79,6 +79,13 @@ class Stop(C.Structure):
     ]
 
 
+# ... the listed mode of the three ask/tell handles (checked by tests/test_ask_tell_compact_cpu.py): one function per
+# handle type, named by the suffix
+ASK_TELL_COMPACT_SUFFIXES = ("lbfgs", "lbfgs_f32", "lbfgsb")
+ASK_TELL_COMPACT_SYMBOLS = ["mi355_ask_tell_%s_%s" % (call, suffix) for call in ("compact", "ids")
+                            for suffix in ASK_TELL_COMPACT_SUFFIXES]
+
+
 # ... and the trust-region solver's (checked by tests/test_trust_region_twin.py)
 TRUST_REGION_SYMBOLS = ["mi355_trust_region_default_config", "mi355_trust_region_newton_minimize_batch",
                         "mi355_trust_region_newton_minimize_batch_host"]
@@ -290,6 +297,9 @@ def _bind(L):
         getattr(L, prefix + "destroy").argtypes = [vp]
     L.mi355_lbfgsb_ask_tell_create.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, C.c_int64, vp, vp, C.POINTER(vp)]
     L.mi355_lbfgsb_ask_tell_asks.argtypes = [vp, C.POINTER(C.c_int64), vp]
+    for suffix in ASK_TELL_COMPACT_SUFFIXES:
+        getattr(L, "mi355_ask_tell_compact_" + suffix).argtypes = [vp, C.POINTER(C.c_int64), vp]
+        getattr(L, "mi355_ask_tell_ids_" + suffix).argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     L.mi355_bfgs_minimize_batch.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mi355_bfgs_minimize_batch_host.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp]
     L.mi355_trust_region_default_config.argtypes = [C.POINTER(TrustRegionConfig)]

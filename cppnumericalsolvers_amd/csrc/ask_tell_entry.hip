@@ -2,7 +2,8 @@
 // mi355_lbfgs_ask_tell_* (Lbfgs in double), mi355_lbfgs_ask_tell_f32_* (Lbfgs in float) and mi355_lbfgsb_ask_tell_*
 // (Lbfgsb).  Each path is its traits, its handle struct, its own refusals and its C functions; the rest —
 // the shared refusals, the one device allocation and its layout, the bodies of the entry points — is ask_tell_host.hpp.
-// The kernels are behind dispatch_lbfgs_ask_tell.hip, dispatch_lbfgs_ask_tell_f32.hip and dispatch_lbfgsb_ask_tell.hip.
+// The kernels are behind dispatch_lbfgs_ask_tell.hip, dispatch_lbfgs_ask_tell_f32.hip and dispatch_lbfgsb_ask_tell.hip,
+// those of a compacted handle (mi355_ask_tell_compact_*) behind their *_listed.hip twins and dispatch_ask_tell_compact.hip.
 #include "ask_tell_host.hpp"
 #include "lbfgs_ask_tell_config.hpp"
 #include "lbfgs_ask_tell_f32_config.hpp"
@@ -21,6 +22,8 @@ struct LbfgsPath {
   using ResultArgs = ask_tell::ResultArgs;
   static long long row(int m, int P) { return ask_tell::row_doubles(m, P); }
   static constexpr auto step = &dispatch_ask_tell_step;
+  static constexpr auto listed_step = &dispatch_ask_tell_listed_step;
+  static constexpr int kFinished = ask_tell::kPhaseFinished;
   static constexpr auto results = &dispatch_ask_tell_results;
   static constexpr const char* kPrefix = "Lbfgs ask/tell";
   static constexpr const char* kWhat = "ask/tell";
@@ -34,6 +37,8 @@ struct LbfgsF32Path {
   using ResultArgs = ask_tell_f32::ResultArgs;
   static long long row(int m, int P) { return ask_tell_f32::row_floats(m, P); }
   static constexpr auto step = &dispatch_ask_tell_f32_step;
+  static constexpr auto listed_step = &dispatch_ask_tell_f32_listed_step;
+  static constexpr int kFinished = ask_tell_f32::kPhaseFinished;
   static constexpr auto results = &dispatch_ask_tell_f32_results;
   static constexpr const char* kPrefix = "Lbfgs ask/tell f32";
   static constexpr const char* kWhat = "ask/tell f32";
@@ -49,6 +54,11 @@ struct LbfgsbPath {
   static int step(mi355_lbfgs_ctx* ctx, int, int E, const Args& a, hipStream_t stream) {  // (W is kLanes)
     return dispatch_ask_tell_box_step(ctx, E, a, stream);
   }
+  static int listed_step(mi355_lbfgs_ctx* ctx, int, int E, const Args& a, const long long* ids, long long listed,
+                         hipStream_t stream) {
+    return dispatch_ask_tell_box_listed_step(ctx, E, a, ids, listed, stream);
+  }
+  static constexpr int kFinished = ask_tell_box::kPhaseFinished;
   static constexpr auto results = &dispatch_ask_tell_box_results;
   static constexpr const char* kPrefix = "Lbfgsb ask/tell";
   static constexpr const char* kWhat = "ask/tell";
@@ -250,5 +260,25 @@ int mi355_lbfgsb_ask_tell_results(mi355_lbfgsb_ask_tell* handle, double* x_out, 
   return host::results(handle, x_out, f_out, g_out, progress_out, stream);
 }
 int mi355_lbfgsb_ask_tell_destroy(mi355_lbfgsb_ask_tell* handle) { return host::destroy(handle); }
+
+// ---- the list of the live problems, for the three handle types ----------------------------------------------------------
+int mi355_ask_tell_compact_lbfgs(mi355_lbfgs_ask_tell* handle, int64_t* listed_host, void* stream) {
+  return host::compact(handle, listed_host, stream);
+}
+int mi355_ask_tell_compact_lbfgs_f32(mi355_lbfgs_ask_tell_f32* handle, int64_t* listed_host, void* stream) {
+  return host::compact(handle, listed_host, stream);
+}
+int mi355_ask_tell_compact_lbfgsb(mi355_lbfgsb_ask_tell* handle, int64_t* listed_host, void* stream) {
+  return host::compact(handle, listed_host, stream);
+}
+int mi355_ask_tell_ids_lbfgs(mi355_lbfgs_ask_tell* handle, const int64_t** ids_dev, int64_t* listed) {
+  return host::ids(handle, ids_dev, listed);
+}
+int mi355_ask_tell_ids_lbfgs_f32(mi355_lbfgs_ask_tell_f32* handle, const int64_t** ids_dev, int64_t* listed) {
+  return host::ids(handle, ids_dev, listed);
+}
+int mi355_ask_tell_ids_lbfgsb(mi355_lbfgsb_ask_tell* handle, const int64_t** ids_dev, int64_t* listed) {
+  return host::ids(handle, ids_dev, listed);
+}
 
 }  // extern "C"

@@ -7,6 +7,8 @@
 //   Scalar, Scalars, Args, ResultArgs   the types of its *_config.hpp
 //   row(m, P)                           scalars of one problem's state row at padded width P
 //   step(ctx, W, E, args, stream), results(result_args, stream)   the calls into its dispatch unit
+//   listed_step(ctx, W, E, args, ids, listed, stream)             ... and into its unit of listed step kernels
+//   kFinished                           the phase word of a finished problem (what a compaction drops)
 //   kPrefix                             what its refusals start with ("Lbfgs ask/tell", ...)
 //   kWhat                               how its HIP failures name the state ("ask/tell", "ask/tell f32")
 // and by its public handle struct H, which derives from Handle<T> and, where the defaults of Handle do not do, adds the
@@ -19,11 +21,37 @@
 #include "engine_internal.hpp"
 
 namespace mi355 {
+
+// The compaction of a handle's list (ask_tell_compact_kernel.hpp, behind dispatch_ask_tell_compact.hip).
+namespace ask_tell_compact {
+
+constexpr int kGroup = 64;  // list entries per workgroup of the count and scatter kernels: one wavefront
+
+template <class Scalar, class Scalars>
+struct Args {
+  const Scalars* scalars;  // [B], by problem: the phase words
+  const long long* ids;    // [listed] the current list, ascending; nullptr: the identity (never compacted)
+  long long* ids_next;     // [<= listed] the kept problems
+  const Scalar* rows;      // [listed][n] the evaluation buffer, by slot
+  Scalar* rows_next;       // [<= listed][n] the kept rows
+  long long* counts;       // [groups + 1]: keep count per group, then their exclusive scan; [groups] = the total
+  long long listed;
+  int n;
+};
+
+}  // namespace ask_tell_compact
+
+// the three launches; instantiated for the three paths in dispatch_ask_tell_compact.hip
+template <class Scalar, class Scalars, int kFinished>
+int dispatch_ask_tell_compact(const ask_tell_compact::Args<Scalar, Scalars>& args, hipStream_t stream);
+
 namespace ask_tell_host {
 
 // One solve in flight: the state of all B problems in ONE device allocation,
 //   [ vectors B row | x_eval B n | scalars B | the path's extras | counters: active, then the path's ]
-// every part at a multiple of 16 bytes (carve()).
+// every part at a multiple of 16 bytes (carve()).  A handle that has been compacted (compact()) holds a second one,
+//   [ ids B | ids B | rows B n | counts ceil(B / 64) + 1 ]
+// the two id lists (the current one and the next), the packed rows of a compaction and its group counts.
 template <class T>
 struct Handle {
   using Traits = T;
@@ -38,6 +66,14 @@ struct Handle {
   int64_t B = 0;
   int n = 0, m = 0, W = 0, E = 0;  // W lanes per problem at E coordinates per lane
   mi355_lbfgs_stop stop = {};
+  // listed mode, from the first compact() on: slot s < listed of x_eval / f / g belongs to problem ids[s]
+  bool listed_mode = false;
+  int64_t listed = 0;
+  char* list_block = nullptr;
+  long long* ids = nullptr;  // the current list: one of ids_buffer; nullptr when B == 0
+  long long* ids_buffer[2] = {nullptr, nullptr};
+  Scalar* rows_next = nullptr;
+  long long* counts = nullptr;
 
   // what a path without extras needs: the active counter alone, nothing between the scalars and the counters, and
   // step arguments that are the common ones
@@ -213,11 +249,16 @@ int x(H* handle, const typename H::Scalar** x_eval) {
 template <class H>
 int step(H* handle, const typename H::Scalar* f, const typename H::Scalar* g, int64_t* active_host, void* stream_) {
   if (!handle) return fail(MI355_ERR_INVALID_ARGUMENT, "null handle");
-  if (handle->B > 0 && (!f || !g)) return fail(MI355_ERR_INVALID_ARGUMENT, "null f / g");
+  // the rows the caller evaluated: all B, or the list of a compacted handle (f [listed], g [listed][n])
+  const int64_t rows = handle->listed_mode ? handle->listed : handle->B;
+  if (rows > 0 && (!f || !g)) return fail(MI355_ERR_INVALID_ARGUMENT, "null f / g");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   MI355_ENTER_DEVICE(handle->ctx);
-  if (handle->B > 0) {
-    const int rc = H::Traits::step(handle->ctx, handle->W, handle->E, step_args(handle, f, g), stream);
+  if (rows > 0) {
+    const int rc = handle->listed_mode
+                       ? H::Traits::listed_step(handle->ctx, handle->W, handle->E, step_args(handle, f, g), handle->ids,
+                                                handle->listed, stream)
+                       : H::Traits::step(handle->ctx, handle->W, handle->E, step_args(handle, f, g), stream);
     if (rc != MI355_OK) return rc;
   }
   if (active_host) {
@@ -226,6 +267,88 @@ int step(H* handle, const typename H::Scalar* f, const typename H::Scalar* g, in
     HIP_TRY(hipStreamSynchronize(stream));
     *active_host = static_cast<int64_t>(count);
   }
+  return MI355_OK;
+}
+
+// The second allocation of a handle, made at its first compaction.  On failure the handle is as it was.
+template <class H>
+int allocate_list(H* h) {
+  const auto round16 = [](size_t bytes) { return (bytes + 15) & ~static_cast<size_t>(15); };
+  const size_t B = static_cast<size_t>(h->B);
+  const size_t id_bytes = round16(B * sizeof(long long));
+  const size_t row_bytes = round16(B * h->n * sizeof(typename H::Scalar));
+  const size_t groups = (B + ask_tell_compact::kGroup - 1) / ask_tell_compact::kGroup;
+  const size_t bytes = 2 * id_bytes + row_bytes + (groups + 1) * sizeof(long long);
+  char* block = nullptr;
+  const hipError_t e = hipMalloc(reinterpret_cast<void**>(&block), bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(MI355_ERR_HIP, std::string("hipMalloc of the ") + H::Traits::kWhat + " list (" + std::to_string(bytes) +
+                                   " bytes): " + hipGetErrorString(e));
+  }
+  h->list_block = block;
+  h->ids_buffer[0] = reinterpret_cast<long long*>(block);
+  h->ids_buffer[1] = reinterpret_cast<long long*>(block + id_bytes);
+  h->rows_next = reinterpret_cast<typename H::Scalar*>(block + 2 * id_bytes);
+  h->counts = reinterpret_cast<long long*>(block + 2 * id_bytes + row_bytes);
+  return MI355_OK;
+}
+
+// Rebuilds the list: of the problems listed now (all B before the first call), those that have not finished, in
+// ascending order, with their rows of x_eval packed to the front.  Waits for the stream; from here on the handle is in
+// listed mode.
+template <class H>
+int compact(H* handle, int64_t* listed_host, void* stream_) {
+  using T = typename H::Traits;
+  if (!handle || !listed_host) return fail(MI355_ERR_INVALID_ARGUMENT, "null argument");
+  const int64_t current = handle->listed_mode ? handle->listed : handle->B;
+  if (current == 0) {  // an empty batch, or everything has finished: nothing to launch
+    handle->listed_mode = true;
+    handle->listed = 0;
+    *listed_host = 0;
+    return MI355_OK;
+  }
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  MI355_ENTER_DEVICE(handle->ctx);
+  if (!handle->list_block) {
+    const int rc = allocate_list(handle);
+    if (rc != MI355_OK) return rc;
+  }
+  long long* const next = (handle->ids == handle->ids_buffer[0]) ? handle->ids_buffer[1] : handle->ids_buffer[0];
+  ask_tell_compact::Args<typename H::Scalar, typename T::Scalars> a;
+  a.scalars = handle->scalars;
+  a.ids = handle->listed_mode ? handle->ids : nullptr;
+  a.ids_next = next;
+  a.rows = handle->x_eval;
+  a.rows_next = handle->rows_next;
+  a.counts = handle->counts;
+  a.listed = current;
+  a.n = handle->n;
+  const int rc = dispatch_ask_tell_compact<typename H::Scalar, typename T::Scalars, T::kFinished>(a, stream);
+  if (rc != MI355_OK) return rc;
+  const long long groups = (current + ask_tell_compact::kGroup - 1) / ask_tell_compact::kGroup;
+  long long total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, handle->counts + groups, sizeof(total), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (total < 0 || total > current) return fail(MI355_ERR_HIP, "internal: the compaction kept more than was listed");
+  if (total > 0)  // the packed rows back into the evaluation buffer, whose pointer the caller holds
+    HIP_TRY(hipMemcpyAsync(handle->x_eval, handle->rows_next,
+                           static_cast<size_t>(total) * handle->n * sizeof(typename H::Scalar), hipMemcpyDeviceToDevice,
+                           stream));
+  handle->ids = next;
+  handle->listed = total;
+  handle->listed_mode = true;
+  *listed_host = total;
+  return MI355_OK;
+}
+
+// The list of a compacted handle: DEVICE [listed], ascending.  Before the first compaction: nullptr and B.
+template <class H>
+int ids(H* handle, const int64_t** ids_dev, int64_t* listed) {
+  if (!handle || !ids_dev || !listed) return fail(MI355_ERR_INVALID_ARGUMENT, "null argument");
+  static_assert(sizeof(long long) == sizeof(int64_t), "the list is handed out as int64_t");
+  *ids_dev = handle->listed_mode ? reinterpret_cast<const int64_t*>(handle->ids) : nullptr;
+  *listed = handle->listed_mode ? handle->listed : handle->B;
   return MI355_OK;
 }
 
@@ -262,7 +385,9 @@ template <class H>
 int destroy(H* handle) {
   if (!handle) return MI355_OK;
   MI355_ENTER_DEVICE(handle->ctx);
-  const hipError_t e = hipFree(handle->block);  // (waits for the device: no kernel still reads the state)
+  hipError_t e = hipFree(handle->block);  // (waits for the device: no kernel still reads the state)
+  const hipError_t e_list = hipFree(handle->list_block);  // (nullptr: a handle that was never compacted)
+  if (e == hipSuccess) e = e_list;
   delete handle;
   if (e != hipSuccess)
     return fail(MI355_ERR_HIP, std::string("hipFree of the ") + H::Traits::kWhat + " state: " + hipGetErrorString(e));
@@ -274,24 +399,26 @@ int destroy(H* handle) {
 // The step launch of the three dispatch units.  kern: a __global__ function taking the path's Args, one wavefront per
 // workgroup, W lanes per problem at E coordinates per lane; dynamic_lds: its dynamic LDS bytes (0: none, and the
 // kernel's limit is left alone); reported_lds: what last_launch() says (the static LDS of a kernel without dynamic).
-// A grid-stride loop over the batch: as many workgroups as the chip holds (or the batch needs).
-template <int W, int E, class Kernel, class Args>
-int launch_ask_tell_step(mi355_lbfgs_ctx* ctx, Kernel kern, int dynamic_lds, int reported_lds, const Args& args,
-                         hipStream_t stream) {
+// A grid-stride loop over `rows` rows of the caller's arrays — the batch, or the list of a compacted handle, whose
+// kernel takes the list after the path's Args (`more`) —: as many workgroups as the chip holds (or the rows need).
+template <int W, int E, class Kernel, class Args, class... More>
+int launch_ask_tell_rows(mi355_lbfgs_ctx* ctx, Kernel kern, int dynamic_lds, int reported_lds, long long rows,
+                         const Args& args, hipStream_t stream, const More&... more) {
   constexpr int kSegs = kWave / W;
   if (args.n > W * E) return fail(MI355_ERR_INVALID_ARGUMENT, "internal: the lane mapping does not cover n");
+  if (rows < 1 || rows > args.B) return fail(MI355_ERR_INVALID_ARGUMENT, "internal: the rows of a step do not fit the batch");
   if (dynamic_lds > 0)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, dynamic_lds));
   int per_cu = 0;
   HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kWave, dynamic_lds));
   if (per_cu < 1) per_cu = 1;
-  const long long blocks_needed = (args.B + kSegs - 1) / kSegs;
+  const long long blocks_needed = (rows + kSegs - 1) / kSegs;
   long long blocks_ll = static_cast<long long>(per_cu) * ctx->num_cus;
   if (ctx->debug_blocks >= 1 && ctx->debug_blocks < blocks_ll) blocks_ll = ctx->debug_blocks;
   if (blocks_ll > blocks_needed) blocks_ll = blocks_needed;
   HIP_TRY(hipMemsetAsync(args.active, 0, sizeof(unsigned long long), stream));
   HIP_TRY(hipEventRecord(ctx->ev_start, stream));
-  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks_ll)), dim3(kWave), dynamic_lds, stream, args);
+  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks_ll)), dim3(kWave), dynamic_lds, stream, args, more...);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ctx->ev_stop, stream));
   ctx->timed = true;
@@ -304,6 +431,13 @@ int launch_ask_tell_step(mi355_lbfgs_ctx* ctx, Kernel kern, int dynamic_lds, int
   ctx->last_variant = MI355_KERNEL_GENERAL;
   ctx->last_arith = MI355_ARITH_EXACT;
   return MI355_OK;
+}
+
+// ... over the whole batch: the step of a handle that has not been compacted
+template <int W, int E, class Kernel, class Args>
+int launch_ask_tell_step(mi355_lbfgs_ctx* ctx, Kernel kern, int dynamic_lds, int reported_lds, const Args& args,
+                         hipStream_t stream) {
+  return launch_ask_tell_rows<W, E>(ctx, kern, dynamic_lds, reported_lds, args.B, args, stream);
 }
 
 // kern(args...) with one thread per element, `total` = B n of them: the state initialisations and the result gathers

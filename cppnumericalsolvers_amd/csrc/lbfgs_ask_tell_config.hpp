@@ -68,5 +68,9 @@ struct ResultArgs {
 int dispatch_ask_tell_step(mi355_lbfgs_ctx* ctx, int W, int E, const ask_tell::Args& args, hipStream_t stream);
 int dispatch_ask_tell_init(const ask_tell::Args& args, const double* x0, long long row, hipStream_t stream);
 int dispatch_ask_tell_results(const ask_tell::ResultArgs& args, hipStream_t stream);
+// dispatch_lbfgs_ask_tell_listed.hip: the step kernel of a compacted handle in the same six mappings — slot s < listed
+// of x_eval / f / g belongs to problem ids[s]
+int dispatch_ask_tell_listed_step(mi355_lbfgs_ctx* ctx, int W, int E, const ask_tell::Args& args, const long long* ids,
+                                  long long listed, hipStream_t stream);
 
 }  // namespace mi355

@@ -70,5 +70,9 @@ struct ResultArgs {
 int dispatch_ask_tell_f32_step(mi355_lbfgs_ctx* ctx, int W, int E, const ask_tell_f32::Args& args, hipStream_t stream);
 int dispatch_ask_tell_f32_init(const ask_tell_f32::Args& args, const float* x0, long long row, hipStream_t stream);
 int dispatch_ask_tell_f32_results(const ask_tell_f32::ResultArgs& args, hipStream_t stream);
+// dispatch_lbfgs_ask_tell_f32_listed.hip: the step kernel of a compacted handle in the same six mappings — slot
+// s < listed of x_eval / f / g belongs to problem ids[s]
+int dispatch_ask_tell_f32_listed_step(mi355_lbfgs_ctx* ctx, int W, int E, const ask_tell_f32::Args& args,
+                                      const long long* ids, long long listed, hipStream_t stream);
 
 }  // namespace mi355

@@ -42,10 +42,13 @@ __device__ __forceinline__ void segment_fence() {
   __builtin_amdgcn_wave_barrier();
 }
 
-// One step of problem `prob` on the calling segment.  sy_l / alpha_l: MI355_LBFGS_MAX_M floats of LDS of this segment.
-// Returns whether the problem is still active after the call.
+// One step of problem `prob` on the calling segment.  `slot`: its row of the caller's arrays (x_eval, f, g) — `prob`
+// itself, or its place in the list of a compacted handle (ask_tell_compact_kernel.hpp); everything else is indexed by
+// `prob`.  sy_l / alpha_l: MI355_LBFGS_MAX_M floats of LDS of this segment.  Returns whether the problem is still
+// active after the call.
 template <int W, int E>
-__device__ __forceinline__ bool step_problem(const Args& a, long long prob, int sl, float* sy_l, float* alpha_l) {
+__device__ __forceinline__ bool step_problem(const Args& a, long long prob, long long slot, int sl, float* sy_l,
+                                             float* alpha_l) {
   using namespace f32;
   constexpr int P = W * E;
   const float eps = std::numeric_limits<float>::epsilon();
@@ -70,7 +73,7 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, int 
   float* const ds = row + 2 * P;
   float* const Ss = row + 3 * P;
   float* const Ys = Ss + static_cast<long long>(m) * P;
-  const long long base = prob * n + sl * E;  // of the caller's [B][n] arrays
+  const long long base = slot * n + sl * E;  // of the caller's [B][n] arrays
 
   float x[E], g[E], d[E];
   float f = zero, scaling_factor = one, x_delta = zero, f_delta = zero, gradient_norm = zero;
@@ -135,7 +138,7 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, int 
       x[e] = in ? a.x_eval[base + e] : zero;
       g[e] = in ? a.g[base + e] : zero;
     }
-    f = a.f[prob];
+    f = a.f[slot];
     nfev = 1;  // the fetch of lbfgs_f32_kernel.hpp: everything else is the initial value above
 #pragma unroll
     for (int e = 0; e < E; ++e) {
@@ -164,7 +167,7 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, int 
         d[e] = ds[e];
         g[e] = (sl * E + e < n) ? a.g[base + e] : zero;
       }
-      f = a.f[prob];
+      f = a.f[slot];
       stx = sc->stx; fx = sc->fx; dgx = sc->dgx;
       sty = sc->sty; fy = sc->fy; dgy = sc->dgy;
       stp = sc->stp; width = sc->width; width1 = sc->width1;
@@ -459,7 +462,29 @@ __global__ __launch_bounds__(64) void step_kernel(const Args a) {
   for (long long first = static_cast<long long>(blockIdx.x) * kSegs; first < a.B; first += stride) {
     const long long prob = first + seg;
     bool active = false;
-    if (prob < a.B) active = step_problem<W, E>(a, prob, sl, sy_lds[seg], alpha_lds[seg]);
+    if (prob < a.B) active = step_problem<W, E>(a, prob, prob, sl, sy_lds[seg], alpha_lds[seg]);
+    active_count += __builtin_popcountll(__builtin_amdgcn_ballot_w64(active && sl == 0));
+  }
+  if (lane == 0 && active_count != 0) atomicAdd(a.active, active_count);
+}
+
+// The same step on a compacted handle (a kernel of its own: step_kernel stays as it was built before there were lists):
+// slot s of x_eval / f / g belongs to problem ids[s], ids ascending.  a.B is the LENGTH OF THE LIST here (nothing of a
+// step is indexed by the batch size), and the grid is sized from it.
+template <int W, int E>
+__global__ __launch_bounds__(64) void listed_step_kernel(const Args a, const long long* ids) {
+  constexpr int kSegs = kWave / W;
+  __shared__ float sy_lds[kSegs][MI355_LBFGS_MAX_M];
+  __shared__ float alpha_lds[kSegs][MI355_LBFGS_MAX_M];
+  const int lane = threadIdx.x;
+  const int seg = lane / W;
+  const int sl = lane % W;
+  unsigned long long active_count = 0;  // wavefront-uniform
+  const long long stride = static_cast<long long>(gridDim.x) * kSegs;
+  for (long long first = static_cast<long long>(blockIdx.x) * kSegs; first < a.B; first += stride) {
+    const long long slot = first + seg;
+    bool active = false;
+    if (slot < a.B) active = step_problem<W, E>(a, ids[slot], slot, sl, sy_lds[seg], alpha_lds[seg]);
     active_count += __builtin_popcountll(__builtin_amdgcn_ballot_w64(active && sl == 0));
   }
   if (lane == 0 && active_count != 0) atomicAdd(a.active, active_count);

@@ -38,10 +38,13 @@ __device__ __forceinline__ void segment_fence() {
   __builtin_amdgcn_wave_barrier();
 }
 
-// One step of problem `prob` on the calling segment.  rho_l / alpha_l: MI355_LBFGS_MAX_M (+ 1) doubles of LDS of this
-// segment.  Returns whether the problem is still active after the call.
+// One step of problem `prob` on the calling segment.  `slot`: its row of the caller's arrays (x_eval, f, g) — `prob`
+// itself, or its place in the list of a compacted handle (ask_tell_compact_kernel.hpp); everything else is indexed by
+// `prob`.  rho_l / alpha_l: MI355_LBFGS_MAX_M (+ 1) doubles of LDS of this segment.  Returns whether the problem is
+// still active after the call.
 template <int W, int E>
-__device__ __forceinline__ bool step_problem(const Args& a, long long prob, int sl, double* rho_l, double* alpha_l) {
+__device__ __forceinline__ bool step_problem(const Args& a, long long prob, long long slot, int sl, double* rho_l,
+                                             double* alpha_l) {
   using AR = ArithExact;
   constexpr int P = W * E;
   constexpr double eps = 2.220446049250313e-16;  // numeric_limits<double>::epsilon()
@@ -61,7 +64,7 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, int 
   double* const ds = row + 2 * P;
   double* const Ss = row + 3 * P;
   double* const Ys = Ss + static_cast<long long>(m) * P;
-  const long long base = prob * n + sl * E;  // of the caller's [B][n] arrays
+  const long long base = slot * n + sl * E;  // of the caller's [B][n] arrays
 
   double x[E], g[E], d[E];
   double f = 0.0, scaling_factor = 1.0, xinf_bound = 0.0, x_delta = 0.0, f_delta = 0.0, gradient_norm = 0.0;
@@ -130,7 +133,7 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, int 
       x[e] = in ? a.x_eval[base + e] : 0.0;
       g[e] = in ? a.g[base + e] : 0.0;
     }
-    f = a.f[prob];
+    f = a.f[slot];
     nfev = 1;                               // reset_solver of lbfgs_kernel.hpp: everything else is the initial value above
     xinf_bound = seg_amax<W, E>(x);
   } else {
@@ -154,7 +157,7 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, int 
         d[e] = ds[e];
         gn[e] = (sl * E + e < n) ? a.g[base + e] : 0.0;
       }
-      fn = a.f[prob];
+      fn = a.f[slot];
       stx = sc->stx; fx = sc->fx; dgx = sc->dgx;
       sty = sc->sty; fy = sc->fy; dgy = sc->dgy;
       stp = sc->stp; width = sc->width; width1 = sc->width1;
@@ -417,7 +420,29 @@ __global__ __launch_bounds__(64) void step_kernel(const Args a) {
   for (long long first = static_cast<long long>(blockIdx.x) * kSegs; first < a.B; first += stride) {
     const long long prob = first + seg;
     bool active = false;
-    if (prob < a.B) active = step_problem<W, E>(a, prob, sl, rho_lds[seg], alpha_lds[seg]);
+    if (prob < a.B) active = step_problem<W, E>(a, prob, prob, sl, rho_lds[seg], alpha_lds[seg]);
+    active_count += __builtin_popcountll(__builtin_amdgcn_ballot_w64(active && sl == 0));
+  }
+  if (lane == 0 && active_count != 0) atomicAdd(a.active, active_count);
+}
+
+// The same step on a compacted handle (a kernel of its own: step_kernel stays as it was built before there were lists):
+// slot s of x_eval / f / g belongs to problem ids[s], ids ascending.  a.B is the LENGTH OF THE LIST here (nothing of a
+// step is indexed by the batch size), and the grid is sized from it.
+template <int W, int E>
+__global__ __launch_bounds__(64) void listed_step_kernel(const Args a, const long long* ids) {
+  constexpr int kSegs = kWave / W;
+  __shared__ double rho_lds[kSegs][MI355_LBFGS_MAX_M];
+  __shared__ double alpha_lds[kSegs][MI355_LBFGS_MAX_M + 1];
+  const int lane = threadIdx.x;
+  const int seg = lane / W;
+  const int sl = lane % W;
+  unsigned long long active_count = 0;  // wavefront-uniform
+  const long long stride = static_cast<long long>(gridDim.x) * kSegs;
+  for (long long first = static_cast<long long>(blockIdx.x) * kSegs; first < a.B; first += stride) {
+    const long long slot = first + seg;
+    bool active = false;
+    if (slot < a.B) active = step_problem<W, E>(a, ids[slot], slot, sl, rho_lds[seg], alpha_lds[seg]);
     active_count += __builtin_popcountll(__builtin_amdgcn_ballot_w64(active && sl == 0));
   }
   if (lane == 0 && active_count != 0) atomicAdd(a.active, active_count);

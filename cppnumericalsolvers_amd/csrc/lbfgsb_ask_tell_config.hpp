@@ -119,6 +119,10 @@ struct InitArgs {
 int dispatch_ask_tell_box_step(mi355_lbfgs_ctx* ctx, int E, const ask_tell_box::Args& args, hipStream_t stream);
 int dispatch_ask_tell_box_init(const ask_tell_box::InitArgs& args, hipStream_t stream);
 int dispatch_ask_tell_box_results(const ask_tell_box::ResultArgs& args, hipStream_t stream);
+// dispatch_lbfgsb_ask_tell_listed.hip: the step kernel of a compacted handle at the same (E, capacity) — slot
+// s < listed of x_eval / f / g belongs to problem ids[s]; the state, the scalars and the boxes stay by problem
+int dispatch_ask_tell_box_listed_step(mi355_lbfgs_ctx* ctx, int E, const ask_tell_box::Args& args, const long long* ids,
+                                      long long listed, hipStream_t stream);
 constexpr int ask_tell_box_capacity(int m) { return m <= 5 ? 5 : 8; }
 
 }  // namespace mi355

@@ -33,10 +33,12 @@
 namespace mi355 {
 namespace ask_tell_box {
 
-// One step of problem `prob` on the calling segment.  `base`: the LDS of this segment, lbfgsb_lds_doubles_per_problem<M>
-// doubles in the layout of lbfgsb_solve_kernel.  Returns the Ask the problem leaves with, kAskNothing, or kNotActive.
+// One step of problem `prob` on the calling segment.  `slot`: its row of the caller's arrays (x_eval, f, g) — `prob`
+// itself, or its place in the list of a compacted handle (ask_tell_compact_kernel.hpp); the state, the scalars and the
+// box are indexed by `prob`.  `base`: the LDS of this segment, lbfgsb_lds_doubles_per_problem<M> doubles in the layout
+// of lbfgsb_solve_kernel.  Returns the Ask the problem leaves with, kAskNothing, or kNotActive.
 template <int E, int M>
-__device__ __forceinline__ int step_problem(const Args& a, long long prob, int sl, double* base) {
+__device__ __forceinline__ int step_problem(const Args& a, long long prob, long long slot, int sl, double* base) {
   using AR = ArithExact;
   constexpr int W = kLanes;
   constexpr int P = W * E;
@@ -71,7 +73,7 @@ __device__ __forceinline__ int step_problem(const Args& a, long long prob, int s
   double* const Sg = Yg + static_cast<long long>(mcap) * P;
   double* const Ag = Sg + static_cast<long long>(mcap) * P;
   double* const SSg = Ag + M * M;
-  const long long cbase = prob * n + sl * E;  // of the caller's [B][n] arrays
+  const long long cbase = slot * n + sl * E;  // of the caller's [B][n] arrays
 
   double lo[E], hi[E];
   {
@@ -189,7 +191,7 @@ __device__ __forceinline__ int step_problem(const Args& a, long long prob, int s
     // ---- Minimize's prologue (:253) + InitializeSolver (:120-139): the caller's f, g are the evaluation at x0 --------
     load_vec(Xr, x);  // (x0, put there by the state initialisation)
     load_caller_g(g);
-    f = a.f[prob];
+    f = a.f[slot];
     nfev = 1;  // reset_solver of lbfgsb_kernel.hpp: everything else is the initial value above
     stage = kStartStep;
   } else {
@@ -203,7 +205,7 @@ __device__ __forceinline__ int step_problem(const Args& a, long long prob, int s
       // ---- the evaluation at clip(x) (:151-153) ----------------------------------------------------------------------
       load_vec(Xr, x);
       load_caller_g(g);
-      f = a.f[prob];
+      f = a.f[slot];
       nfev++;
       stage = kDirection;
     } else {
@@ -215,7 +217,7 @@ __device__ __forceinline__ int step_problem(const Args& a, long long prob, int s
         double d[E], gn[E];
         load_vec(Dr, d);
         load_caller_g(gn);
-        const double fn = a.f[prob];
+        const double fn = a.f[slot];
         stx = sc->stx; fx = sc->fx; dgx = sc->dgx;
         sty = sc->sty; fy = sc->fy; dgy = sc->dgy;
         stp = sc->stp; width = sc->width; width1 = sc->width1;
@@ -280,7 +282,7 @@ __device__ __forceinline__ int step_problem(const Args& a, long long prob, int s
         // ---- the evaluation at the Cauchy point (:191-193) or at clip(next.x) (:199-203): the point is vector D -------
         load_vec(Dr, x);
         load_caller_g(g);
-        f = a.f[prob];
+        f = a.f[slot];
         nfev++;
         stage = (phase == kPhaseCauchy) ? kAfterSearch : kUpdate;
       }
@@ -948,7 +950,40 @@ __global__ __launch_bounds__(64) void step_kernel(const Args a) {
   for (long long first = static_cast<long long>(blockIdx.x) * kSegs; first < a.B; first += stride) {
     const long long prob = first + seg;
     int ask = kNotActive;
-    if (prob < a.B) ask = step_problem<E, M>(a, prob, sl, base);
+    if (prob < a.B) ask = step_problem<E, M>(a, prob, prob, sl, base);
+    const bool lead = sl == 0;
+    active_count += __builtin_popcountll(__builtin_amdgcn_ballot_w64(lead && ask != kNotActive));
+#pragma unroll
+    for (int kind = 0; kind < kAskKinds - 1; ++kind)
+      ask_count[kind] += __builtin_popcountll(__builtin_amdgcn_ballot_w64(lead && ask == kind));
+  }
+  if (lane == 0) {
+    if (active_count != 0) atomicAdd(a.active, active_count);
+#pragma unroll
+    for (int kind = 0; kind < kAskKinds - 1; ++kind)
+      if (ask_count[kind] != 0) atomicAdd(a.asks + kind, ask_count[kind]);
+  }
+}
+
+// The same step on a compacted handle (a kernel of its own: step_kernel stays as it was built before there were lists):
+// slot s of x_eval / f / g belongs to problem ids[s], ids ascending.  a.B is the LENGTH OF THE LIST here (nothing of a
+// step is indexed by the batch size), and the grid is sized from it.
+template <int E, int M>
+__global__ __launch_bounds__(64) void listed_step_kernel(const Args a, const long long* ids) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  constexpr int W = kLanes;
+  constexpr int kSegs = kWave / W;
+  const int lane = threadIdx.x;
+  const int seg = lane / W;
+  const int sl = lane % W;
+  double* const base = lds + seg * lbfgsb_lds_doubles_per_problem<M>(W * E, 0);
+  unsigned long long active_count = 0;  // wavefront-uniform
+  unsigned long long ask_count[kAskKinds - 1] = {0, 0, 0, 0};
+  const long long stride = static_cast<long long>(gridDim.x) * kSegs;
+  for (long long first = static_cast<long long>(blockIdx.x) * kSegs; first < a.B; first += stride) {
+    const long long slot = first + seg;
+    int ask = kNotActive;
+    if (slot < a.B) ask = step_problem<E, M>(a, ids[slot], slot, sl, base);
     const bool lead = sl == 0;
     active_count += __builtin_popcountll(__builtin_amdgcn_ballot_w64(lead && ask != kNotActive));
 #pragma unroll
@@ -965,7 +1000,9 @@ __global__ __launch_bounds__(64) void step_kernel(const Args a) {
 
 // x0 into the evaluation buffer and into vector X of the state row (whose padding and scalars the host has zeroed: phase
 // "first evaluation pending"), so that results() before the first step returns the start point; the caller's box — or
-// the reference's default one — into the handle's copy, with a flag raised for a NaN bound
+// the reference's default one — into the handle's copy, with a flag raised for a NaN bound.  (Not a template: it is
+// defined in one unit only, dispatch_lbfgsb_ask_tell.hip; the unit of the listed step kernels leaves it out.)
+#ifndef MI355_ASK_TELL_LISTED_TU
 __global__ void init_kernel(const InitArgs a) {
   const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (t >= a.B * a.n) return;
@@ -989,6 +1026,7 @@ __global__ void init_kernel(const InitArgs a) {
     a.upper[at] = hi;
   }
 }
+#endif
 
 // (the result gather is ask_tell_kernel_common.hpp's)
 

@@ -419,7 +419,7 @@ class BatchedLbfgs:
             self._stream()))
         return x0
 
-    def minimize_callable(self, fn, x0, check_every=1, max_rounds=None):
+    def minimize_callable(self, fn, x0, check_every=1, max_rounds=None, compact_every=None):
         """Batched Solver::Minimize of an objective the CALLER evaluates (ask/tell, `LbfgsAskTell`): `fn(X)` takes the
         [B, n] CUDA tensor of the points to evaluate (of the solver's dtype: float64, or float32 on the native float
         path of BatchedLbfgs) and returns (f [B], g [B, n]) of that dtype — or f alone, and the gradient
@@ -427,25 +427,54 @@ class BatchedLbfgs:
         sum's gradient is the per-problem gradient; in float32 autograd differentiates in float32).  X is the solver's own buffer: read it, do not keep or write it.
         check_every=k reads the active count back every k rounds (a round on a finished batch changes nothing);
         max_rounds: RuntimeError when the batch is still active after that many rounds.
+        compact_every=k (None: off, and everything above is the whole story): the loop keeps the LIST of the problems
+        that have not finished (`LbfgsAskTell.compact`), rebuilt every k rounds, and calls `fn(X, ids)` with X [listed, n]
+        — the points of the listed problems only — and ids [listed] int64, their numbers, ascending: an objective with
+        per-problem data indexes it by ids, and a finished problem costs no evaluation after the next compaction.  f is
+        [listed], g [listed, n] (or f alone, as above).  The loop ends when a compaction lists nothing; check_every is
+        ignored then: the active count is read every round, so fn runs exactly as many rounds as with check_every=1.
+        The results are those of the loop without a list, bit for bit.
+        A compaction is three small kernels, a read-back and a copy of the kept rows (about 37 us): k = 1 drops a
+        finished problem at once, a larger k spreads that cost over k rounds.  Measured on 65 536 x Rosenbrock-32
+        (profiles/ask_tell_compact_rounds.txt): fn sees 15.7 % of batch x rounds at k = 1 and 16.1 % at k = 16; with
+        the cheapest fn there is (one small kernel) no k beats the loop without a list at check_every=16, and k = 16 or
+        64 beats check_every=1 by 4 - 6 %.  Use k = 16 when fn's cost grows with its rows; leave it None when fn is cheap.
         Returns (x, f, g, progress) like `minimize`."""
         if int(check_every) < 1:
             raise ValueError("check_every must be >= 1")
+        if compact_every is not None and int(compact_every) < 1:
+            raise ValueError("compact_every must be >= 1 (None: no list)")
         torch = self._torch
         value_only = [None]   # which of the two forms fn has: the first round tells
 
-        def evaluate(X):
+        def evaluate(X, *ids):
             if value_only[0] is None:
                 with torch.no_grad():
-                    out = fn(X)
+                    out = fn(X, *ids)
                 value_only[0] = not isinstance(out, (tuple, list))
                 if not value_only[0]:
                     return out
             if not value_only[0]:
-                return fn(X)
+                return fn(X, *ids)
             leaf = X.detach().requires_grad_(True)
-            f = fn(leaf)
+            f = fn(leaf, *ids)
             (g,) = torch.autograd.grad(f.sum(), leaf)
             return f.detach(), g
+
+        if compact_every is not None:
+            with self._ask_tell(x0) as at:
+                rounds = 0
+                while at.compact() > 0:
+                    for _ in range(int(compact_every)):
+                        f, g = evaluate(at.x, at.ids)
+                        rounds += 1
+                        active = at.tell(f, g)   # (read every round: fn is never called on a finished batch)
+                        if active == 0:
+                            break
+                        if max_rounds is not None and rounds >= int(max_rounds):
+                            raise RuntimeError("minimize_callable: %d problems still active after max_rounds = %d rounds"
+                                               % (active, int(max_rounds)))
+                return at.results()
 
         with self._ask_tell(x0) as at:
             rounds = 0
@@ -522,6 +551,7 @@ class LbfgsAskTell:
     _prefix = "mi355_lbfgs_ask_tell_"
 
     _prefix_f32 = "mi355_lbfgs_ask_tell_f32_"   # the handle type of a float32 solver
+    _listed_suffix = "lbfgs"                    # mi355_ask_tell_compact_lbfgs[_f32], mi355_ask_tell_ids_lbfgs[_f32]
 
     def _call(self, name, *args):
         capi.check(getattr(self._lib, (self._prefix_f32 if self._f32 else self._prefix) + name)(*args))
@@ -556,9 +586,10 @@ class LbfgsAskTell:
         self._h = h
         p = C.c_void_p()
         self._call("x", self._h, C.byref(p))
-        self.x = torch.as_tensor(_DeviceArray(p.value, (self.B, self.n), "<f4" if self._f32 else "<f8", self),
-                                 device=solver.device) \
-            if self.B > 0 else torch.empty(0, self.n, dtype=self._dtype, device=solver.device)
+        self._x_ptr = p.value
+        self.ids = None          # compact(): the [listed] int64 view of the list
+        self._listed = self.B    # rows of .x / f / g: B, or the length of the list
+        self.x = self._x_view(self.B)
         self._call("active", self._h, C.byref(p))
         self._active_dev = torch.as_tensor(_DeviceArray(p.value, (1,), "<i8", self), device=solver.device)
 
@@ -569,14 +600,48 @@ class LbfgsAskTell:
         self.solver._on_device(t, what)
         return t.detach().contiguous()
 
+    def _x_view(self, rows):
+        """the first `rows` rows of the evaluation buffer as a tensor VIEW"""
+        torch = self.solver._torch
+        if rows == 0:
+            return torch.empty(0, self.n, dtype=self._dtype, device=self.solver.device)
+        return torch.as_tensor(_DeviceArray(self._x_ptr, (rows, self.n), "<f4" if self._f32 else "<f8", self),
+                               device=self.solver.device)
+
+    def _call_listed(self, name, *args):
+        """mi355_ask_tell_<name>_<handle type>: the calls of the listed mode"""
+        suffix = self._listed_suffix + ("_f32" if self._f32 else "")
+        capi.check(getattr(self._lib, "mi355_ask_tell_%s_%s" % (name, suffix))(*args))
+
+    def compact(self):
+        """Rebuilds the list of the problems that have not finished (mi355_ask_tell_compact_*; waits for the stream) and
+        returns its length `listed`.  Afterwards .ids is the [listed] int64 view of the problems' numbers, ascending, .x
+        the [listed, n] view of the SAME buffer — row s is the point to evaluate for problem ids[s] — and tell() takes
+        f [listed], g [listed, n].  A problem that finishes later stays listed until the next compact().  results() is
+        always all B problems, in problem order, and equals the uncompacted solve's bit for bit."""
+        if self._h is None:
+            raise RuntimeError("this %s is closed" % type(self).__name__)
+        torch = self.solver._torch
+        count = C.c_int64(-1)
+        self._call_listed("compact", self._h, C.byref(count), self.solver._stream())
+        p, listed = C.c_void_p(), C.c_int64(-1)
+        self._call_listed("ids", self._h, C.byref(p), C.byref(listed))
+        self._listed = int(listed.value)
+        assert self._listed == int(count.value)
+        self.x = self._x_view(self._listed)
+        self.ids = torch.as_tensor(_DeviceArray(p.value, (self._listed,), "<i8", self), device=self.solver.device) \
+            if self._listed > 0 else torch.empty(0, dtype=torch.int64, device=self.solver.device)
+        return self._listed
+
     def tell(self, f, g, wait=True):
         """Hands the values f [B] and gradients g [B, n] at the rows of .x to the solver and advances every problem to
-        its next evaluation.  wait=True: returns the number of problems still active (waits for the stream);
+        its next evaluation (after compact(): f [listed], g [listed, n], and only the listed problems run).
+        wait=True: returns the number of problems still active (waits for the stream);
         wait=False: returns None and nothing waits (`.active` reads the count later)."""
         if self._h is None:
             raise RuntimeError("this %s is closed" % type(self).__name__)
-        f = self._rows(f, (self.B,), "f")
-        g = self._rows(g, (self.B, self.n), "g")
+        f = self._rows(f, (self._listed,), "f")
+        g = self._rows(g, (self._listed, self.n), "g")
         count = C.c_int64(-1)
         self._call("step", self._h, f.data_ptr(), g.data_ptr(), C.byref(count) if wait else None, self.solver._stream())
         return int(count.value) if wait else None
@@ -606,7 +671,7 @@ class LbfgsAskTell:
         """Frees the device state (waits for the device); .x must not be used afterwards."""
         if getattr(self, "_h", None) is not None:
             h, self._h = self._h, None
-            self.x = self._active_dev = None
+            self.x = self.ids = self._active_dev = None
             self._call("destroy", h)
 
     def __enter__(self):
@@ -907,6 +972,7 @@ class LbfgsbAskTell(LbfgsAskTell):
     copied at creation.  `.asks`: how many problems asked for each kind of evaluation so far.  Built for n <= 64, m <= 8,
     the More-Thuente search and the reference-order arithmetic (arithmetic="default" is that here; "fma" is refused)."""
     _prefix = "mi355_lbfgsb_ask_tell_"
+    _listed_suffix = "lbfgsb"
     ASK_KINDS = ("clip_start", "trial", "cauchy", "clip_next", "first")
 
     def _check_solver(self, solver):

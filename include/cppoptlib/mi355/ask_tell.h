@@ -11,6 +11,8 @@
 //                       (mi355_lbfgsb_ask_tell_*), plus Asks(), the count of every kind of evaluation asked for
 //   MinimizeBatchWith   the loop around either: evaluator(x_dev, f_dev, g_dev, B, n) is the user's — its own kernels,
 //                       hipBLAS, anything that leaves f [B] and g [B][n] in device memory, ordered on `stream`.
+//   Compact(), Ids()    on the three handles: the listed mode (mi355_ask_tell_compact_*), in which the caller evaluates
+//                       only the problems that have not finished; MinimizeBatchWithCompaction is the loop around it.
 //
 // Plain C++17: no HIP header is needed here; the device arrays are the caller's.  Failures surface through Fail()
 // (context.h): an exception, or abort() when built with -fno-exceptions.
@@ -60,6 +62,8 @@ struct LbfgsAskTellApi {
   static constexpr auto active = &mi355_lbfgs_ask_tell_active;
   static constexpr auto results = &mi355_lbfgs_ask_tell_results;
   static constexpr auto destroy = &mi355_lbfgs_ask_tell_destroy;
+  static constexpr auto compact = &mi355_ask_tell_compact_lbfgs;
+  static constexpr auto ids = &mi355_ask_tell_ids_lbfgs;
   static constexpr const char* kClass = "LbfgsAskTell";
   static constexpr const char* kPrefix = "mi355_lbfgs_ask_tell_";
 };
@@ -72,6 +76,8 @@ struct LbfgsAskTellF32Api {
   static constexpr auto active = &mi355_lbfgs_ask_tell_f32_active;
   static constexpr auto results = &mi355_lbfgs_ask_tell_f32_results;
   static constexpr auto destroy = &mi355_lbfgs_ask_tell_f32_destroy;
+  static constexpr auto compact = &mi355_ask_tell_compact_lbfgs_f32;
+  static constexpr auto ids = &mi355_ask_tell_ids_lbfgs_f32;
   static constexpr const char* kClass = "LbfgsAskTellF32";
   static constexpr const char* kPrefix = "mi355_lbfgs_ask_tell_f32_";
 };
@@ -84,6 +90,8 @@ struct LbfgsbAskTellApi {
   static constexpr auto active = &mi355_lbfgsb_ask_tell_active;
   static constexpr auto results = &mi355_lbfgsb_ask_tell_results;
   static constexpr auto destroy = &mi355_lbfgsb_ask_tell_destroy;
+  static constexpr auto compact = &mi355_ask_tell_compact_lbfgsb;
+  static constexpr auto ids = &mi355_ask_tell_ids_lbfgsb;
   static constexpr const char* kClass = "LbfgsbAskTell";
   static constexpr const char* kPrefix = "mi355_lbfgsb_ask_tell_";
 };
@@ -131,6 +139,29 @@ class AskTellHandle {
   void Results(Scalar* x_dev, Scalar* f_dev, Scalar* g_dev, mi355_lbfgs_progress* progress_dev) const {
     Checked(Api::results(handle_, x_dev, f_dev, g_dev, progress_dev, stream_), "results");
   }
+  // Listed mode (mi355_ask_tell_compact_*): rebuilds the list of the problems that have not finished and returns its
+  // length.  From the first call on, row s < listed of Ask() is the point to evaluate for problem Ids()[s], and Tell /
+  // TellAsync take f_dev [listed], g_dev [listed][n].  Waits for the stream.  Results() stays all B problems in order.
+  int64_t Compact() {
+    int64_t listed = 0;
+    CheckedListed(Api::compact(handle_, &listed, stream_), "compact");
+    return listed;
+  }
+  // DEVICE [listed()]: the numbers of the listed problems, ascending (valid until the next Compact()); nullptr before
+  // the first Compact()
+  const int64_t* Ids() const {
+    const int64_t* p = nullptr;
+    int64_t listed = 0;
+    CheckedListed(Api::ids(handle_, &p, &listed), "ids");
+    return p;
+  }
+  // the rows of Ask() / Tell(): the length of the list, batch() before the first Compact()
+  int64_t listed() const {
+    const int64_t* p = nullptr;
+    int64_t listed = 0;
+    CheckedListed(Api::ids(handle_, &p, &listed), "ids");
+    return listed;
+  }
   int64_t batch() const { return B_; }
   int dimension() const { return n_; }
   void* stream() const { return stream_; }
@@ -147,6 +178,10 @@ class AskTellHandle {
   // Check() under the C function's full name, put together only when the call failed
   static void Checked(int rc, const char* function) {
     if (rc != MI355_OK) Check(rc, (std::string(Api::kPrefix) + function).c_str());
+  }
+  // ... for the calls of the listed mode, named mi355_ask_tell_<function>_<handle type>
+  static void CheckedListed(int rc, const char* function) {
+    if (rc != MI355_OK) Check(rc, (std::string("mi355_ask_tell_") + function + " (" + Api::kClass + ")").c_str());
   }
 
   std::shared_ptr<Context> context_;
@@ -243,6 +278,33 @@ int64_t MinimizeBatchWith(Evaluator&& evaluator, Handle& solve, typename Handle:
     if (max_rounds >= 0 && rounds >= max_rounds)
       Fail("MinimizeBatchWith: " + std::to_string(active) + " problems still active after max_rounds = " +
            std::to_string(max_rounds) + " rounds");
+  }
+}
+
+// The same loop over the LIST of the problems that have not finished, rebuilt every compact_every >= 1 rounds:
+// evaluator(x_dev, f_dev, g_dev, rows, n, ids_dev) evaluates the `rows` listed problems only — x_dev [rows][n] their
+// points, ids_dev [rows] their numbers (ascending, for per-problem data), f_dev [rows] and g_dev [rows][n] its output —
+// so a finished problem costs no evaluation after the next compaction.  The work arrays hold B rows.  The active count
+// is read every round and the loop ends with the batch: the number of rounds, and every bit of the results, are
+// MinimizeBatchWith's.  Returns the number of rounds.
+template <class Evaluator, class Handle>
+int64_t MinimizeBatchWithCompaction(Evaluator&& evaluator, Handle& solve, typename Handle::Scalar* f_dev,
+                                    typename Handle::Scalar* g_dev, int64_t compact_every = 1, int64_t max_rounds = -1) {
+  if (compact_every < 1) Fail("MinimizeBatchWithCompaction: compact_every must be >= 1");
+  int64_t rounds = 0;
+  while (true) {
+    const int64_t rows = solve.Compact();
+    if (rows == 0) return rounds;
+    const int64_t* const ids = solve.Ids();
+    for (int64_t k = 0; k < compact_every; ++k) {
+      evaluator(solve.Ask(), f_dev, g_dev, rows, solve.dimension(), ids);
+      ++rounds;
+      const int64_t active = solve.Tell(f_dev, g_dev);
+      if (active == 0) return rounds;
+      if (max_rounds >= 0 && rounds >= max_rounds)
+        Fail("MinimizeBatchWithCompaction: " + std::to_string(active) + " problems still active after max_rounds = " +
+             std::to_string(max_rounds) + " rounds");
+    }
   }
 }
 

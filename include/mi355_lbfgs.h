@@ -758,6 +758,32 @@ int mi355_lbfgsb_ask_tell_destroy(mi355_lbfgsb_ask_tell* handle);
 /* counts_host: HOST, 5 counters; waits for `stream`. */
 int mi355_lbfgsb_ask_tell_asks(mi355_lbfgsb_ask_tell* handle, int64_t counts_host[5], void* stream);
 
+/* ---- ask/tell, listed mode: the caller evaluates the live problems only (opt-in; additive, the ABI number stays) ------
+ * A batch runs as many rounds as its slowest problem needs, and without a list the caller evaluates all B rows in every
+ * one of them.  _compact rebuilds the handle's LIST: the problems whose phase is not "finished", strictly ascending (a
+ * problem that wants no evaluation in the coming round stays listed), and packs their rows of the evaluation buffer to
+ * the front.  After it returns, slot s < listed of the buffer behind _x (the same pointer as ever; rows at and beyond
+ * `listed` are unspecified) holds the point to evaluate for problem ids[s].  From the first _compact on the handle is in
+ * listed mode: _step(handle, f, g, ...) reads f[s] and g[s n ...] for s < listed, runs the listed problems only (its grid
+ * is sized from `listed`) and writes each problem's next point into slot s.  A problem that finishes between two
+ * compactions stays listed until the next one; as ever its f / g rows are not read and its slot is frozen.  The active
+ * count, _active, _results (always all B problems, in problem order) and _asks keep their meaning; the state, the scalars
+ * and the boxes stay indexed by problem.  The results are those of the handle that is never compacted, bit for bit.
+ * listed_host (HOST, required) receives the length of the list; the call waits for `stream`, as _step with active_host
+ * does.  _compact before the first _step lists all B problems; twice in a row gives the same list; once everything has
+ * finished it returns 0, and a later _step launches nothing and accepts null f / g.  B = 0: MI355_OK with 0.  A null
+ * handle or out-pointer: MI355_ERR_INVALID_ARGUMENT.  The first _compact allocates the lists and the row scratch
+ * (2 B int64, B n scalars, B / 64 + 1 int64; freed by _destroy); if that fails it returns MI355_ERR_HIP and the handle
+ * goes on unlisted.  A handle that is never compacted allocates and launches exactly what it did before.
+ * _ids: the DEVICE list (valid until the next _compact or _destroy) and its length; before the first _compact: NULL and
+ * B.  One function per handle type: ..._lbfgs for mi355_lbfgs_ask_tell, ..._lbfgs_f32 and ..._lbfgsb for the others. */
+int mi355_ask_tell_compact_lbfgs(mi355_lbfgs_ask_tell* handle, int64_t* listed_host, void* stream);
+int mi355_ask_tell_compact_lbfgs_f32(mi355_lbfgs_ask_tell_f32* handle, int64_t* listed_host, void* stream);
+int mi355_ask_tell_compact_lbfgsb(mi355_lbfgsb_ask_tell* handle, int64_t* listed_host, void* stream);
+int mi355_ask_tell_ids_lbfgs(mi355_lbfgs_ask_tell* handle, const int64_t** ids_dev, int64_t* listed);
+int mi355_ask_tell_ids_lbfgs_f32(mi355_lbfgs_ask_tell_f32* handle, const int64_t** ids_dev, int64_t* listed);
+int mi355_ask_tell_ids_lbfgsb(mi355_lbfgsb_ask_tell* handle, const int64_t** ids_dev, int64_t* listed);
+
 /* Duration in ms of the most recent solve kernel on this context, measured with
  * HIP events recorded on the launch stream; blocks until that kernel finished. */
 int mi355_lbfgs_last_kernel_ms(mi355_lbfgs_ctx* ctx, float* ms);

@@ -10,7 +10,14 @@ In one process, after a warm-up of each, `--repeats` times alternating:
                host clock around the whole loop, which ends in a synchronise
 and once more by hand through LbfgsAskTell to record the problems still active after every round.
 Prints a text report and writes it to --out.  No figure is asserted.
-    python scripts/ask_tell_bench.py [--repeats 3] [--batch 65536] [--out profiles/ask_tell_rounds.txt]"""
+    python scripts/ask_tell_bench.py [--repeats 3] [--batch 65536] [--out profiles/ask_tell_rounds.txt]
+
+--compact-every K[,K...] measures the LISTED mode instead: minimize_callable(compact_every=K) for every
+K next to the uncompacted loop with check_every = 1 and 16 IN THE SAME RUN, alternating, after a warm-up of each (every
+path must return the persistent kernel's bits: checked).  Beside the host-clock times it reports the rounds and the
+deterministic figure the mode exists for: the ROWS the callback evaluated (the sum of `listed` over the rounds) against
+batch x rounds.  That report goes to profiles/ask_tell_compact_rounds.txt unless --out says otherwise.
+    python scripts/ask_tell_bench.py --compact-every 1,4,16,64"""
 import argparse
 import os
 import statistics
@@ -27,8 +34,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--batch", type=int, default=65536)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ask_tell_rounds.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--compact-every", default=None, help="comma-separated K: measure the listed mode (see above)")
     args = ap.parse_args()
+    every = [int(k) for k in args.compact_every.split(",")] if args.compact_every else []
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "ask_tell_compact_rounds.txt" if every else "ask_tell_rounds.txt")
     import torch
     assert torch.cuda.is_available(), "this measurement needs an MI355X"
     import cppnumericalsolvers_amd as amd
@@ -58,6 +69,24 @@ def main():
         out = solver.minimize_callable(fn, x0, check_every=check_every)
         torch.cuda.synchronize()
         return out, (time.perf_counter() - t0) * 1e3, rounds[0]
+
+    def listed(k):
+        rounds, seen = [0], [0]
+
+        def fn(X, ids):
+            rounds[0] += 1
+            seen[0] += X.shape[0]
+            return solver.evaluate(objective, X)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = solver.minimize_callable(fn, x0, compact_every=k)
+        torch.cuda.synchronize()
+        return out, (time.perf_counter() - t0) * 1e3, rounds[0], seen[0]
+
+    if every:
+        compact_report(args, torch, B, n, m, every, persistent, ask_tell, listed)
+        ctx.close()
+        return
 
     want, _, _ = persistent()          # warm-up of every path: code objects, allocator, clocks
     for k in (1, 16):
@@ -115,6 +144,57 @@ def main():
     with open(args.out, "w") as fh:
         fh.write(text)
     ctx.close()
+
+
+def compact_report(args, torch, B, n, m, every, persistent, ask_tell, listed):
+    """the listed mode next to the uncompacted loop, in one run"""
+    want, _, _ = persistent()          # warm-up of every path, and the bits
+    for check in (1, 16):
+        got, _, _ = ask_tell(check)
+        for a, b in zip(got, want):
+            assert torch.equal(a, b), "the uncompacted loop must return the persistent kernel's bits"
+    for k in every:
+        got, _, _, _ = listed(k)
+        for a, b in zip(got, want):
+            assert torch.equal(a, b), "the listed loop must return the persistent kernel's bits"
+    wall = {("check", c): [] for c in (1, 16)}
+    wall.update({("compact", k): [] for k in every})
+    rounds_of, rows_of = {}, {}
+    for _ in range(args.repeats):
+        for c in (1, 16):
+            _, ms, rounds_of[("check", c)] = ask_tell(c)
+            wall[("check", c)].append(ms)
+        for k in every:
+            _, ms, rounds_of[("compact", k)], rows_of[k] = listed(k)
+            wall[("compact", k)].append(ms)
+    med = {key: statistics.median(v) for key, v in wall.items()}
+    base = med[("check", 16)]
+    spread = max((max(v) - min(v)) / statistics.median(v) for v in wall.values())
+    lines = []
+    out = lines.append
+    out("ask/tell L-BFGS, listed mode next to the uncompacted loop: %d x Rosenbrock-%d, m = %d, parity stop, one MI355X" % (B, n, m))
+    out("callback: the library's evaluation entry (every loop returns the persistent kernel's bits: checked); one run,")
+    out("%d alternating repeats after a warm-up of each, host clock around the whole loop, medians [min, max]" % args.repeats)
+    for c in (1, 16):
+        key = ("check", c)
+        out("  uncompacted, check_every = %-2d  %10.3f ms  [%.3f, %.3f]  %5d rounds  rows evaluated %11d (all of batch x rounds)"
+            % (c, med[key], min(wall[key]), max(wall[key]), rounds_of[key], B * rounds_of[key]))
+    for k in every:
+        key = ("compact", k)
+        out("  compact_every = %-3d            %10.3f ms  [%.3f, %.3f]  %5d rounds  rows evaluated %11d (%.1f %% of batch x rounds)  %.3f x check_every = 16"
+            % (k, med[key], min(wall[key]), max(wall[key]), rounds_of[key], rows_of[k],
+               100.0 * rows_of[k] / (B * rounds_of[key]), med[key] / base))
+    out("largest (max - min) / median of a row above: %.1f %%" % (100.0 * spread))
+    faster = [k for k in every if med[("compact", k)] < base * (1.0 - spread)]
+    slower = [k for k in every if k not in faster]
+    out("faster than the uncompacted check_every = 16 loop beyond that spread: compact_every in %s; not faster: %s"
+        % (faster or "none", slower or "none"))
+    out("(the callback here is the cheapest there is; the rows evaluated are what an expensive callback pays for)")
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write(text)
 
 
 if __name__ == "__main__":
