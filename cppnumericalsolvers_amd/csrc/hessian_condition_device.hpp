@@ -17,7 +17,9 @@
 //     chains over the column-major storage: the device's sums round differently in the last bits, so device and twin agree
 //     on the DECISION `condition > threshold` (and on everything downstream of it) unless the condition number sits within
 //     an ulp-scale distance of the threshold; the value itself is not part of the device's output (the host reports it at
-//     the returned x, include/cppoptlib/solver/lbfgs.h ReportHessianCondition).
+//     the returned x, include/cppoptlib/solver/lbfgs.h ReportHessianCondition).  The value is tested all the same:
+//     tests/test_gpu_condition_value.py brackets it between thresholds (2 n^2 + 8) 2^-53 to either side of the twin's,
+//     which is what the two summation orders can differ by, and bisects it to the last bit.
 #pragma once
 #include "wave_primitives.hpp"
 

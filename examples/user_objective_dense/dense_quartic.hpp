@@ -9,7 +9,10 @@
 // Hm[j n + i], so a solver that reads H(j, i) for H(i, j) computes something else whenever S != S^T.
 //     _build.build(output=".../libmi355_lbfgs_tr.so",
 //                  user_objectives=[..., dict(name="dense_quartic", header=<this file>, type="user_examples::DenseQuartic",
-//                                             id=101, lbfgs=False, lbfgsb=False, trust_region=True, newton_descent=True)])
+//                                             id=101, lbfgs=True, lbfgsb=False, trust_region=True, newton_descent=True)])
+// lbfgs=True also builds the Lbfgs kernels: with hessian_from_functor they take the preconditioner from hess_diag and,
+// with the condition_hessian test on, H(x) from hess_full at one or two coordinates per lane — the only place where the
+// condition number's LU meets a dense matrix with two rows of the trailing block per lane.
 // Operation order (tests/newton_descent/nd_twin.hpp, tests/trust_region/tr_twin.hpp and the two reference harnesses state
 // the same), per coordinate i:
 //     sx_i = S(i, 0) x_0, then sx_i = sx_i + S(i, j) x_j for j = 1 .. n - 1           (ascending, first term a product)
@@ -85,6 +88,16 @@ struct DenseQuartic {
     double sx[E];
     times_s<W, E>(x, sx, n, sl);
     return finish<W, E>(x, sx, n, sl);
+  }
+  // diag H(x) for Lbfgs in Second mode (hessian_from_functor: the preconditioner of every iterate): the diagonal of
+  // hess_full, the same operations; padding coordinates 0
+  template <int W, int E>
+  __device__ __forceinline__ void hess_diag(const double (&x)[E], double (&h)[E], int n, int sl) const {
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const int i = sl * E + e;
+      h[e] = (i < n) ? S[i * n + i] + (3.0 * kappa) * (x[e] * x[e]) : 0.0;
+    }
   }
   template <int W, int E>
   __device__ __forceinline__ void hess_full(const double (&x)[E], double* Hm, int n, int sl) const {
