@@ -149,15 +149,17 @@ def mappings_of(n):
 
 
 # ---- trajectories ------------------------------------------------------------------------------------------------------------
-def prefix_trajectories(solve, x0, f0, g0, m):
-    """solve(x0 rows, stop fields) -> (x, f, g, progress) -> [(xs, gs, fs)] per row of x0"""
+def prefix_trajectories(solve, x0, f0, g0, m, fields=None, first_fields=None):
+    """solve(x0 rows, stop fields) -> (x, f, g, progress) -> [(xs, gs, fs)] per row of x0; `fields`, `first_fields`: another
+    stop record than this module's"""
+    fields, first_fields = fields or stop_fields, first_fields or first_iteration_fields
     rows = x0.shape[0]
     out = [([x0[b]], [g0[b]], [f0[b]]) for b in range(rows)]
     running = list(range(rows))
     for k in range(1, limit(m) + 2):
         if not running:
             break
-        x, f, g, p = solve(x0[running], first_iteration_fields() if k == 1 else stop_fields(k - 1))
+        x, f, g, p = solve(x0[running], first_fields() if k == 1 else fields(k - 1))
         still = []
         for i, b in enumerate(running):
             done = int(p["num_iterations"][i])
