@@ -1,7 +1,8 @@
 // ask_tell_host.hpp — the host code the three ask/tell (reverse communication) paths share: Lbfgs in double
 // (mi355_lbfgs_ask_tell_*), Lbfgs in float (mi355_lbfgs_ask_tell_f32_*) and Lbfgsb (mi355_lbfgsb_ask_tell_*).  The
 // handle base with its one device allocation, the refusals common to the three, the entry-point bodies
-// (ask_tell_entry.hip turns them into the C functions) and the two launches of the dispatch units.  No kernel lives here.
+// (ask_tell_entry.hip turns them into the C functions), the two launches of the dispatch units and their choice among the
+// built mappings.  No kernel lives here.
 //
 // A path is described by a traits struct T:
 //   Scalar, Scalars, Args, ResultArgs   the types of its *_config.hpp
@@ -17,6 +18,7 @@
 #include <memory>
 #include <new>
 #include <string>
+#include <type_traits>
 
 #include "engine_internal.hpp"
 
@@ -438,6 +440,52 @@ template <int W, int E, class Kernel, class Args>
 int launch_ask_tell_step(mi355_lbfgs_ctx* ctx, Kernel kern, int dynamic_lds, int reported_lds, const Args& args,
                          hipStream_t stream) {
   return launch_ask_tell_rows<W, E>(ctx, kern, dynamic_lds, reported_lds, args.B, args, stream);
+}
+
+// ... over the list of a compacted handle: kern takes the list after the path's Args and reads its length from Args::B
+template <int W, int E, class Kernel, class Args>
+int launch_ask_tell_listed(mi355_lbfgs_ctx* ctx, Kernel kern, int dynamic_lds, int reported_lds, const Args& args,
+                           const long long* ids, long long listed, hipStream_t stream) {
+  if (!ids || listed > args.B) return fail(MI355_ERR_INVALID_ARGUMENT, "internal: a listed step without a list");
+  Args rows = args;
+  rows.B = listed;
+  return launch_ask_tell_rows<W, E>(ctx, kern, dynamic_lds, reported_lds, listed, rows, stream, ids);
+}
+
+// launch(std::integral_constant<int, W>(), std::integral_constant<int, E>()) for the mapping of the call, one of the six
+// the two Lbfgs paths build: 8, 16, 32 or 64 lanes per problem at one coordinate per lane, 64 lanes at two or four.
+// none: the "internal:" line for any other.
+template <class Launch>
+int launch_for_lbfgs_mapping(int W, int E, const char* none, Launch launch) {
+  using One = std::integral_constant<int, 1>;
+  using Wave = std::integral_constant<int, 64>;
+  if (E == 1) {
+    switch (W) {
+      case 8: return launch(std::integral_constant<int, 8>(), One());
+      case 16: return launch(std::integral_constant<int, 16>(), One());
+      case 32: return launch(std::integral_constant<int, 32>(), One());
+      case 64: return launch(Wave(), One());
+    }
+  }
+  if (W == 64 && E == 2) return launch(Wave(), std::integral_constant<int, 2>());
+  if (W == 64 && E == 4) return launch(Wave(), std::integral_constant<int, 4>());
+  return fail(MI355_ERR_UNSUPPORTED, none);
+}
+
+// launch(std::integral_constant<int, E>(), std::integral_constant<int, M>()) for the Lbfgsb path: one, two or four
+// coordinates per lane of its sixteen-lane segment at history capacity M = 5 or 8 (`capacity`: ask_tell_box_capacity(m))
+template <class Launch>
+int launch_for_box_mapping(int E, int capacity, Launch launch) {
+  const auto at = [&](auto e) {
+    if (capacity == 5) return launch(e, std::integral_constant<int, 5>());
+    return launch(e, std::integral_constant<int, 8>());
+  };
+  switch (E) {
+    case 1: return at(std::integral_constant<int, 1>());
+    case 2: return at(std::integral_constant<int, 2>());
+    case 4: return at(std::integral_constant<int, 4>());
+  }
+  return fail(MI355_ERR_UNSUPPORTED, "internal: no Lbfgsb ask/tell kernel for this number of coordinates per lane");
 }
 
 // kern(args...) with one thread per element, `total` = B n of them: the state initialisations and the result gathers

@@ -7,29 +7,13 @@
 #include "lbfgs_ask_tell_kernel.hpp"
 
 namespace mi355 {
-namespace {
-
-template <int W, int E>
-int launch_step(mi355_lbfgs_ctx* ctx, const ask_tell::Args& args, hipStream_t stream) {
-  // static LDS: 1 / (s.y) and the recursion's alpha per segment
-  constexpr int kLds = (kWave / W) * (2 * MI355_LBFGS_MAX_M + 1) * static_cast<int>(sizeof(double));
-  return launch_ask_tell_step<W, E>(ctx, ask_tell::step_kernel<W, E>, 0, kLds, args, stream);
-}
-
-}  // namespace
 
 int dispatch_ask_tell_step(mi355_lbfgs_ctx* ctx, int W, int E, const ask_tell::Args& args, hipStream_t stream) {
-  if (E == 1) {
-    switch (W) {
-      case 8: return launch_step<8, 1>(ctx, args, stream);
-      case 16: return launch_step<16, 1>(ctx, args, stream);
-      case 32: return launch_step<32, 1>(ctx, args, stream);
-      case 64: return launch_step<64, 1>(ctx, args, stream);
-    }
-  }
-  if (W == 64 && E == 2) return launch_step<64, 2>(ctx, args, stream);
-  if (W == 64 && E == 4) return launch_step<64, 4>(ctx, args, stream);
-  return fail(MI355_ERR_UNSUPPORTED, "internal: no ask/tell kernel for this (W, E)");
+  return launch_for_lbfgs_mapping(W, E, "internal: no ask/tell kernel for this (W, E)", [&](auto w, auto e) {
+    constexpr int kW = decltype(w)::value, kE = decltype(e)::value;
+    return launch_ask_tell_step<kW, kE>(ctx, ask_tell::step_kernel<kW, kE>, 0, ask_tell::step_lds_bytes<kW>(), args,
+                                        stream);
+  });
 }
 
 int dispatch_ask_tell_init(const ask_tell::Args& args, const double* x0, long long row, hipStream_t stream) {

@@ -7,31 +7,46 @@
 #include "lbfgsb_ask_tell_kernel.hpp"
 
 namespace mi355 {
-namespace {
+namespace ask_tell_box {
 
-template <int E, int M>
-int launch_step(mi355_lbfgs_ctx* ctx, const ask_tell_box::Args& args, hipStream_t stream) {
-  constexpr int W = ask_tell_box::kLanes;
-  if (args.n > W * E || args.m > M) return fail(MI355_ERR_INVALID_ARGUMENT, "internal: the kernel does not cover n / m");
-  const int lds = (kWave / W) * lbfgsb_lds_doubles_per_problem<M>(W * E, 0) * static_cast<int>(sizeof(double));
-  return launch_ask_tell_step<W, E>(ctx, ask_tell_box::step_kernel<E, M>, lds, lds, args, stream);
+// x0 into the evaluation buffer and into vector X of the state row (whose padding and scalars the host has zeroed: phase
+// "first evaluation pending"), so that results() before the first step returns the start point; the caller's box — or
+// the reference's default one — into the handle's copy, with a flag raised for a NaN bound.  (Not a template, so it
+// lives in the one unit that launches it, not in the kernel header the unit of the listed step kernels includes too.)
+__global__ void init_kernel(const InitArgs a) {
+  const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (t >= a.B * a.n) return;
+  const long long b = t / a.n;
+  const int j = static_cast<int>(t - b * a.n);
+  const double v = a.x0[t];
+  a.x_eval[t] = v;
+  a.vectors[b * a.row + j] = v;
+  if (j == 0) a.scalars[b].status = MI355_STATUS_NOT_STARTED;
+  if (t == 0) a.asks[kAskFirst] = static_cast<unsigned long long>(a.B);
+  const bool rows = a.box_stride_in != 0;
+  if (rows || b == 0) {
+    double lo = -1.7976931348623157e308, hi = 1.7976931348623157e308;  // lowest() .. max() (lbfgsb.h:124-129)
+    if (a.lower_in != nullptr) {
+      lo = a.lower_in[b * a.box_stride_in + j];
+      hi = a.upper_in[b * a.box_stride_in + j];
+    }
+    if (lo != lo || hi != hi) *a.nan_flag = 1;
+    const long long at = rows ? t : j;
+    a.lower[at] = lo;
+    a.upper[at] = hi;
+  }
 }
 
-template <int E>
-int by_capacity(mi355_lbfgs_ctx* ctx, const ask_tell_box::Args& args, hipStream_t stream) {
-  if (ask_tell_box_capacity(args.m) == 5) return launch_step<E, 5>(ctx, args, stream);
-  return launch_step<E, 8>(ctx, args, stream);
-}
-
-}  // namespace
+}  // namespace ask_tell_box
 
 int dispatch_ask_tell_box_step(mi355_lbfgs_ctx* ctx, int E, const ask_tell_box::Args& args, hipStream_t stream) {
-  switch (E) {
-    case 1: return by_capacity<1>(ctx, args, stream);
-    case 2: return by_capacity<2>(ctx, args, stream);
-    case 4: return by_capacity<4>(ctx, args, stream);
-  }
-  return fail(MI355_ERR_UNSUPPORTED, "internal: no Lbfgsb ask/tell kernel for this number of coordinates per lane");
+  return launch_for_box_mapping(E, ask_tell_box_capacity(args.m), [&](auto e, auto m) {
+    constexpr int kE = decltype(e)::value, kM = decltype(m)::value;
+    if (args.n > ask_tell_box::kLanes * kE || args.m > kM)
+      return fail(MI355_ERR_INVALID_ARGUMENT, "internal: the kernel does not cover n / m");
+    const int lds = ask_tell_box::step_lds_bytes<kE, kM>();
+    return launch_ask_tell_step<ask_tell_box::kLanes, kE>(ctx, ask_tell_box::step_kernel<kE, kM>, lds, lds, args, stream);
+  });
 }
 
 int dispatch_ask_tell_box_init(const ask_tell_box::InitArgs& args, hipStream_t stream) {

@@ -3,9 +3,10 @@
 // next objective evaluation, and the CALLER evaluates the batch of float trial points and hands float f, g back.
 //
 // The phase machine is that of lbfgs_ask_tell_kernel.hpp; the STATEMENTS are those of lbfgs_f32_kernel.hpp and of the
-// float mt_cvsrch / mt_cstep (more_thuente_f32_device.hpp) on the same operands in the same order, cut at the objective
-// evaluation, so a callback that evaluates with the library's own float functor reproduces the persistent float kernel
-// bit for bit.  What that means against the fp64 ask/tell kernel:
+// float mt_cvsrch / mt_cstep (more_thuente_f32_device.hpp; the search cut at its evaluation is MtSearch<float> of
+// more_thuente_resume.hpp) on the same operands in the same order, cut at the objective evaluation, so a callback that
+// evaluates with the library's own float functor reproduces the persistent float kernel bit for bit.  What that means
+// against the fp64 ask/tell kernel:
 //   * s.y is stored per ring slot, not 1 / (s.y); the |s.y| < eps skip is a real skip and rho = one / denom is formed
 //     inside both loops of the recursion;
 //   * the pair test s.y > eps ||s|| ||y|| is evaluated as written; there is no bound shortcut and no running bound on
@@ -29,7 +30,7 @@
 
 #include "lbfgs_ask_tell_f32_config.hpp"
 #include "lbfgs_f32_kernel.hpp"
-#include "more_thuente_f32_device.hpp"
+#include "more_thuente_resume.hpp"
 #include "wave_primitives_f32.hpp"
 #include "ask_tell_kernel_common.hpp"
 
@@ -53,14 +54,6 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, long
   constexpr int P = W * E;
   const float eps = std::numeric_limits<float>::epsilon();
   const float zero = static_cast<float>(0), one = static_cast<float>(1);
-  // more_thuente.h:140-147
-  const float xtol = static_cast<float>(1e-15);
-  const float ftol = static_cast<float>(1e-4);
-  const float gtol = static_cast<float>(0.9);
-  const float stpmin = static_cast<float>(1e-15);
-  const float stpmax = static_cast<float>(1e15);
-  const float xtrapf = static_cast<float>(4);
-  constexpr int maxfev = 20;
 
   Scalars* const sc = a.scalars + prob;
   const int phase = sc->phase;
@@ -82,37 +75,14 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, long
   bool past_init = false;
   unsigned nfev = 0, sum_k = 0, num_iterations = 0;
 
-  // the search's scalars (mt_cvsrch), segment-uniform
-  float stx = zero, fx = zero, dgx = zero, sty = zero, fy = zero, dgy = zero, stp = zero;
-  float width = zero, width1 = zero, finit = zero, dginit = zero, stmin = zero, stmax = zero;
-  bool brackt = false, stage1 = true;
-  int infoc = 1, ls_nfev = 0;
-  // more_thuente.h:179-195: the interval, the clamp and the fallback before an evaluation
-  auto before_evaluation = [&]() {
-    if (brackt) {
-      stmin = fmin_std(stx, sty);
-      stmax = fmax_std(stx, sty);
-    } else {
-      stmin = stx;
-      stmax = stp + xtrapf * (stp - stx);
-    }
-    stp = fclamp_std(stp, stpmin, stpmax);
-    if ((brackt && ((stp <= stmin) || (stp >= stmax))) || (ls_nfev >= maxfev - 1) || (infoc == 0) ||
-        (brackt && ((stmax - stmin) <= (xtol * stmax)))) {
-      stp = stx;
-    }
-  };
+  MtSearch<float> mt;  // the running search, segment-uniform
   // the trial point wa + stp s = x - stp d into the evaluation buffer, and the search's scalars
   auto ask_trial = [&]() {
 #pragma unroll
     for (int e = 0; e < E; ++e)
-      if (sl * E + e < n) a.x_eval[base + e] = x[e] - stp * d[e];
+      if (sl * E + e < n) a.x_eval[base + e] = x[e] - mt.stp * d[e];
     if (sl == 0) {
-      sc->stx = stx; sc->fx = fx; sc->dgx = dgx;
-      sc->sty = sty; sc->fy = fy; sc->dgy = dgy;
-      sc->stp = stp; sc->width = width; sc->width1 = width1;
-      sc->finit = finit; sc->dginit = dginit; sc->stmin = stmin; sc->stmax = stmax;
-      sc->brackt = brackt; sc->stage1 = stage1; sc->infoc = infoc; sc->ls_nfev = ls_nfev;
+      mt.store(sc);
       sc->nfev = nfev;
       sc->phase = kPhaseTrial;
     }
@@ -168,46 +138,12 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, long
         g[e] = (sl * E + e < n) ? a.g[base + e] : zero;
       }
       f = a.f[slot];
-      stx = sc->stx; fx = sc->fx; dgx = sc->dgx;
-      sty = sc->sty; fy = sc->fy; dgy = sc->dgy;
-      stp = sc->stp; width = sc->width; width1 = sc->width1;
-      finit = sc->finit; dginit = sc->dginit; stmin = sc->stmin; stmax = sc->stmax;
-      brackt = sc->brackt != 0; stage1 = sc->stage1 != 0; infoc = sc->infoc; ls_nfev = sc->ls_nfev;
-      const float dgtest = ftol * dginit;
-      ls_nfev++;
+      mt.load(sc);
+      // (g.s is reduced ahead of the search's own statements here and handed in as a value: the float step kernel ran
+      // longer with the reduction inside them, the fp64 kernels longer without — profiles/ask_tell_refactor_ab.txt)
       nfev++;
-      const float dg = -seg_dot<W, E>(g, d);  // g.s
-      const float ftest1 = finit + stp * dgtest;
-      int info = 0;
-      if ((brackt & ((stp <= stmin) | (stp >= stmax))) | (infoc == 0)) info = 6;
-      if ((stp == stpmax) & (f <= ftest1) & (dg <= dgtest)) info = 5;
-      if ((stp == stpmin) & ((f > ftest1) | (dg >= dgtest))) info = 4;
-      if (ls_nfev >= maxfev) info = 3;
-      if (brackt & (stmax - stmin <= xtol * stmax)) info = 2;
-      if ((f <= ftest1) & (__builtin_fabsf(dg) <= gtol * (-dginit))) info = 1;
-      if (info == 0) {
-        if (stage1 & (f <= ftest1) & (dg >= fmin_std(ftol, gtol) * dginit)) stage1 = false;
-        const bool modified = stage1 & (f <= fx) & (f > ftest1);
-        f32::StepInterval iv;
-        iv.stx = stx; iv.sty = sty; iv.stp = stp; iv.brackt = brackt; iv.info = infoc;
-        iv.fx = modified ? fx - stx * dgtest : fx;
-        iv.fy = modified ? fy - sty * dgtest : fy;
-        iv.dx = modified ? dgx - dgtest : dgx;
-        iv.dy = modified ? dgy - dgtest : dgy;
-        const float fm = modified ? f - stp * dgtest : f;
-        const float dgm = modified ? dg - dgtest : dg;
-        iv = mt_cstep(iv, fm, dgm, stmin, stmax);
-        stx = iv.stx; sty = iv.sty; stp = iv.stp; brackt = iv.brackt; infoc = iv.info;
-        fx = modified ? iv.fx + stx * dgtest : iv.fx;
-        fy = modified ? iv.fy + sty * dgtest : iv.fy;
-        dgx = modified ? iv.dx + dgtest : iv.dx;
-        dgy = modified ? iv.dy + dgtest : iv.dy;
-        if (brackt) {
-          if (__builtin_fabsf(sty - stx) >= static_cast<float>(0.66) * width1) stp = stx + static_cast<float>(0.5) * (sty - stx);
-          width1 = width;
-          width = __builtin_fabsf(sty - stx);
-        }
-        before_evaluation();
+      const float dg = -seg_dot<W, E>(g, d);
+      if (mt.after_evaluation(f, [dg]() { return dg; }) == 0) {
 #pragma unroll
         for (int e = 0; e < E; ++e) x[e] = xp[e];
         ask_trial();
@@ -215,7 +151,7 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, long
       }
       // the search ended: the accepted point, re-formed from the accepted step (more_thuente_f32_device.hpp:248)
 #pragma unroll
-      for (int e = 0; e < E; ++e) x[e] = xp[e] - stp * d[e];
+      for (int e = 0; e < E; ++e) x[e] = xp[e] - mt.stp * d[e];
     } else {
       // ---- no evaluation wanted: the refused search left x, f, g untouched ------------------------------------------
 #pragma unroll
@@ -408,7 +344,7 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, long
     segment_fence();  // (sy_l and alpha_l are rewritten by the next problem of this segment)
   }
   const float descent_direction = -seg_dot<W, E>(g, d);  // :199; also cvsrch's dginit = g.s with s = -d
-  dginit = descent_direction;
+  float dginit = descent_direction;
   float alpha_init = one;  // :207-213
   if (mem_count == 0) {
     const float dn = __builtin_sqrtf(seg_dot<W, E>(d, d));
@@ -434,48 +370,28 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, long
   }
   // ---- the search starts (more_thuente.h:158-177) and asks for its first trial -----------------------------------------
   store_iteration_scalars(kPhaseTrial);
-  brackt = false;
-  stage1 = true;
-  infoc = 1;
-  ls_nfev = 0;
-  finit = f;
-  width = stpmax - stpmin;
-  width1 = static_cast<float>(2) * width;
-  stx = zero; fx = finit; dgx = dginit;
-  sty = zero; fy = finit; dgy = dginit;
-  stp = alpha_init;
-  before_evaluation();
+  mt.start(f, dginit, alpha_init);
   ask_trial();
   return true;
 }
 
-template <int W, int E>
-__global__ __launch_bounds__(64) void step_kernel(const Args a) {
-  constexpr int kSegs = kWave / W;
-  __shared__ float sy_lds[kSegs][MI355_LBFGS_MAX_M];
-  __shared__ float alpha_lds[kSegs][MI355_LBFGS_MAX_M];
-  const int lane = threadIdx.x;
-  const int seg = lane / W;
-  const int sl = lane % W;
-  unsigned long long active_count = 0;  // wavefront-uniform
-  const long long stride = static_cast<long long>(gridDim.x) * kSegs;
-  for (long long first = static_cast<long long>(blockIdx.x) * kSegs; first < a.B; first += stride) {
-    const long long prob = first + seg;
-    bool active = false;
-    if (prob < a.B) active = step_problem<W, E>(a, prob, prob, sl, sy_lds[seg], alpha_lds[seg]);
-    active_count += __builtin_popcountll(__builtin_amdgcn_ballot_w64(active && sl == 0));
-  }
-  if (lane == 0 && active_count != 0) atomicAdd(a.active, active_count);
+// static LDS of a step kernel, per segment: s.y per ring slot and the alpha of the running recursion
+constexpr int kSyLds = MI355_LBFGS_MAX_M, kAlphaLds = MI355_LBFGS_MAX_M;
+template <int W>
+constexpr int step_lds_bytes() {
+  return (kWave / W) * (kSyLds + kAlphaLds) * static_cast<int>(sizeof(float));
 }
 
-// The same step on a compacted handle (a kernel of its own: step_kernel stays as it was built before there were lists):
-// slot s of x_eval / f / g belongs to problem ids[s], ids ascending.  a.B is the LENGTH OF THE LIST here (nothing of a
-// step is indexed by the batch size), and the grid is sized from it.
-template <int W, int E>
-__global__ __launch_bounds__(64) void listed_step_kernel(const Args a, const long long* ids) {
+// One step of every row a.B counts, and the tally of the problems still active after it.  Dense (kListed false): row
+// r is problem r and a.B the batch.  Listed: row s of x_eval / f / g belongs to problem ids[s], ids ascending, a.B is
+// the LENGTH OF THE LIST (nothing of a step is indexed by the batch size) and the grid is sized from it.  (Why the grid
+// loop is spelled here and not in a function the three paths share: run_steps of lbfgsb_ask_tell_kernel.hpp.)
+template <int W, int E, bool kListed>
+__device__ __forceinline__ void run_steps(const Args a, const long long* ids) {
   constexpr int kSegs = kWave / W;
-  __shared__ float sy_lds[kSegs][MI355_LBFGS_MAX_M];
-  __shared__ float alpha_lds[kSegs][MI355_LBFGS_MAX_M];
+  __shared__ float sy_lds[kSegs][kSyLds];
+  __shared__ float alpha_lds[kSegs][kAlphaLds];
+  static_assert(sizeof(sy_lds) + sizeof(alpha_lds) == step_lds_bytes<W>(), "what the launch reports");
   const int lane = threadIdx.x;
   const int seg = lane / W;
   const int sl = lane % W;
@@ -484,10 +400,21 @@ __global__ __launch_bounds__(64) void listed_step_kernel(const Args a, const lon
   for (long long first = static_cast<long long>(blockIdx.x) * kSegs; first < a.B; first += stride) {
     const long long slot = first + seg;
     bool active = false;
-    if (slot < a.B) active = step_problem<W, E>(a, ids[slot], slot, sl, sy_lds[seg], alpha_lds[seg]);
+    if (slot < a.B) active = step_problem<W, E>(a, kListed ? ids[slot] : slot, slot, sl, sy_lds[seg], alpha_lds[seg]);
     active_count += __builtin_popcountll(__builtin_amdgcn_ballot_w64(active && sl == 0));
   }
   if (lane == 0 && active_count != 0) atomicAdd(a.active, active_count);
+}
+
+// The two entry points of run_steps: two kernels, so that the dense one takes no list argument and tests none.
+template <int W, int E>
+__global__ __launch_bounds__(64) void step_kernel(const Args a) {
+  run_steps<W, E, false>(a, nullptr);
+}
+
+template <int W, int E>
+__global__ __launch_bounds__(64) void listed_step_kernel(const Args a, const long long* ids) {
+  run_steps<W, E, true>(a, ids);
 }
 
 // How the result gather (ask_tell_kernel_common.hpp) finishes a value, as the persistent float kernel returns them: the

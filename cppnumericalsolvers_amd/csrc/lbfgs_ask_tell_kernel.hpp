@@ -5,8 +5,9 @@
 // Device counterpart of the same reference code as lbfgs_kernel.hpp (Solver::Minimize solver/solver.h:181-224,
 // Lbfgs::OptimizationStep solver/lbfgs.h:89-303, MoreThuente::cvsrch linesearch/more_thuente.h:137-256,
 // Progress::Update solver/progress.h:153-327), cut at the objective evaluation: the statements are those of
-// lbfgs_kernel.hpp and mt_cvsrch (more_thuente_device.hpp) on the same operands in the same order, so a callback that
-// evaluates with the library's own functor reproduces the persistent exact kernel bit for bit.
+// lbfgs_kernel.hpp and mt_cvsrch (more_thuente_device.hpp; the search cut at its evaluation is MtSearch<double> of
+// more_thuente_resume.hpp) on the same operands in the same order, so a callback that evaluates with the library's own
+// functor reproduces the persistent exact kernel bit for bit.
 //
 // Mapping: one problem per segment of W lanes, lane sl owns coordinates sl * E + e; every reduction is a segment
 // butterfly of wave_primitives.hpp (the pairwise tree over P = W * E, zero padded).  A workgroup is one wavefront; the
@@ -24,7 +25,7 @@
 // No loop depends on a stopping test firing: the two-loop recursion runs mem_count <= m trips.
 #pragma once
 #include "lbfgs_ask_tell_config.hpp"
-#include "more_thuente_device.hpp"
+#include "more_thuente_resume.hpp"
 #include "progress_device.hpp"
 #include "wave_primitives.hpp"
 #include "ask_tell_kernel_common.hpp"
@@ -48,9 +49,6 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, long
   using AR = ArithExact;
   constexpr int P = W * E;
   constexpr double eps = 2.220446049250313e-16;  // numeric_limits<double>::epsilon()
-  // more_thuente.h:140-147
-  constexpr double xtol = 1e-15, ftol = 1e-4, gtol = 0.9, stpmin = 1e-15, stpmax = 1e15, xtrapf = 4.0;
-  constexpr int maxfev = 20;
 
   Scalars* const sc = a.scalars + prob;
   const int phase = sc->phase;
@@ -73,37 +71,14 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, long
   bool past_init = false;
   unsigned nfev = 0, sum_k = 0, num_iterations = 0;
 
-  // the search's scalars (mt_cvsrch), segment-uniform
-  double stx = 0.0, fx = 0.0, dgx = 0.0, sty = 0.0, fy = 0.0, dgy = 0.0, stp = 0.0;
-  double width = 0.0, width1 = 0.0, finit = 0.0, dginit = 0.0, stmin = 0.0, stmax = 0.0;
-  bool brackt = false, stage1 = true;
-  int infoc = 1, ls_nfev = 0;
-  // more_thuente.h:179-195: the interval, the clamp and the fallback before an evaluation
-  auto before_evaluation = [&]() {
-    if (brackt) {
-      stmin = dmin(stx, sty);
-      stmax = dmax(stx, sty);
-    } else {
-      stmin = stx;
-      stmax = stp + xtrapf * (stp - stx);
-    }
-    stp = dclamp(stp, stpmin, stpmax);
-    if ((brackt && ((stp <= stmin) || (stp >= stmax))) || (ls_nfev >= maxfev - 1) || (infoc == 0) ||
-        (brackt && ((stmax - stmin) <= (xtol * stmax)))) {
-      stp = stx;
-    }
-  };
+  MtSearch<double> mt;  // the running search, segment-uniform
   // the trial point wa + stp s = x - stp d into the evaluation buffer, and the search's scalars
   auto ask_trial = [&]() {
 #pragma unroll
     for (int e = 0; e < E; ++e)
-      if (sl * E + e < n) a.x_eval[base + e] = AR::nmadd(stp, d[e], x[e]);
+      if (sl * E + e < n) a.x_eval[base + e] = AR::nmadd(mt.stp, d[e], x[e]);
     if (sl == 0) {
-      sc->stx = stx; sc->fx = fx; sc->dgx = dgx;
-      sc->sty = sty; sc->fy = fy; sc->dgy = dgy;
-      sc->stp = stp; sc->width = width; sc->width1 = width1;
-      sc->finit = finit; sc->dginit = dginit; sc->stmin = stmin; sc->stmax = stmax;
-      sc->brackt = brackt; sc->stage1 = stage1; sc->infoc = infoc; sc->ls_nfev = ls_nfev;
+      mt.store(sc);
       sc->nfev = nfev;
       sc->phase = kPhaseTrial;
     }
@@ -158,52 +133,14 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, long
         gn[e] = (sl * E + e < n) ? a.g[base + e] : 0.0;
       }
       fn = a.f[slot];
-      stx = sc->stx; fx = sc->fx; dgx = sc->dgx;
-      sty = sc->sty; fy = sc->fy; dgy = sc->dgy;
-      stp = sc->stp; width = sc->width; width1 = sc->width1;
-      finit = sc->finit; dginit = sc->dginit; stmin = sc->stmin; stmax = sc->stmax;
-      brackt = sc->brackt != 0; stage1 = sc->stage1 != 0; infoc = sc->infoc; ls_nfev = sc->ls_nfev;
-      const double dgtest = ftol * dginit;
-      ls_nfev++;
-      nfev++;
-      const double dg = -seg_dot<W, E, AR>(gn, d);  // g.s
-      const double ftest1 = finit + stp * dgtest;
-      int info = 0;
-      if ((brackt & ((stp <= stmin) | (stp >= stmax))) | (infoc == 0)) info = 6;
-      if ((stp == stpmax) & (fn <= ftest1) & (dg <= dgtest)) info = 5;
-      if ((stp == stpmin) & ((fn > ftest1) | (dg >= dgtest))) info = 4;
-      if (ls_nfev >= maxfev) info = 3;
-      if (brackt & (stmax - stmin <= xtol * stmax)) info = 2;
-      if ((fn <= ftest1) & (__builtin_fabs(dg) <= gtol * (-dginit))) info = 1;
-      if (info == 0) {
-        if (stage1 & (fn <= ftest1) & (dg >= dmin(ftol, gtol) * dginit)) stage1 = false;
-        const bool modified = stage1 & (fn <= fx) & (fn > ftest1);
-        StepInterval iv;
-        iv.stx = stx; iv.sty = sty; iv.stp = stp; iv.brackt = brackt; iv.info = infoc; iv.rc = 0;
-        iv.fx = modified ? fx - stx * dgtest : fx;
-        iv.fy = modified ? fy - sty * dgtest : fy;
-        iv.dx = modified ? dgx - dgtest : dgx;
-        iv.dy = modified ? dgy - dgtest : dgy;
-        const double fm = modified ? fn - stp * dgtest : fn;
-        const double dgm = modified ? dg - dgtest : dg;
-        iv = mt_cstep(iv, fm, dgm, stmin, stmax);
-        stx = iv.stx; sty = iv.sty; stp = iv.stp; brackt = iv.brackt; infoc = iv.info;
-        fx = modified ? iv.fx + stx * dgtest : iv.fx;
-        fy = modified ? iv.fy + sty * dgtest : iv.fy;
-        dgx = modified ? iv.dx + dgtest : iv.dx;
-        dgy = modified ? iv.dy + dgtest : iv.dy;
-        if (brackt) {
-          if (__builtin_fabs(sty - stx) >= 0.66 * width1) stp = stx + 0.5 * (sty - stx);
-          width1 = width;
-          width = __builtin_fabs(sty - stx);
-        }
-        before_evaluation();
+      mt.load(sc);
+      if (mt.after_evaluation(fn, [&]() { nfev++; return -seg_dot<W, E, AR>(gn, d); }) == 0) {  // (g.s)
         ask_trial();
         return true;
       }
       // the search ended: the accepted point, re-formed from the accepted step (more_thuente_device.hpp:413)
 #pragma unroll
-      for (int e = 0; e < E; ++e) xn[e] = AR::nmadd(stp, d[e], x[e]);
+      for (int e = 0; e < E; ++e) xn[e] = AR::nmadd(mt.stp, d[e], x[e]);
     } else {
       // ---- no evaluation wanted: the refused search left x, f, g untouched ------------------------------------------
 #pragma unroll
@@ -358,8 +295,8 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, long
     segment_fence();  // (alpha_l is rewritten by the next problem of this segment)
   }
   const double descent_direction = -seg_dot<W, E, AR>(g, d);  // :199; also cvsrch's dginit = g.s with s = -d
-  dginit = descent_direction;
-  double alpha_init = 1.0;                                    // :207-213
+  double dginit = descent_direction;
+  double alpha_init = 1.0;                                  // :207-213
   if (mem_count == 0) {
     const double dn = __builtin_sqrt(seg_dot<W, E, AR>(d, d));
     alpha_init = (dn > eps) ? 1.0 / dn : 1.0;
@@ -392,48 +329,28 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, long
   }
   // ---- the search starts (more_thuente.h:158-177) and asks for its first trial -----------------------------------------
   store_iteration_scalars(kPhaseTrial);
-  brackt = false;
-  stage1 = true;
-  infoc = 1;
-  ls_nfev = 0;
-  finit = f;
-  width = stpmax - stpmin;
-  width1 = 2.0 * width;
-  stx = 0.0; fx = finit; dgx = dginit;
-  sty = 0.0; fy = finit; dgy = dginit;
-  stp = alpha_init;
-  before_evaluation();
+  mt.start(f, dginit, alpha_init);
   ask_trial();
   return true;
 }
 
-template <int W, int E>
-__global__ __launch_bounds__(64) void step_kernel(const Args a) {
-  constexpr int kSegs = kWave / W;
-  __shared__ double rho_lds[kSegs][MI355_LBFGS_MAX_M];
-  __shared__ double alpha_lds[kSegs][MI355_LBFGS_MAX_M + 1];
-  const int lane = threadIdx.x;
-  const int seg = lane / W;
-  const int sl = lane % W;
-  unsigned long long active_count = 0;  // wavefront-uniform
-  const long long stride = static_cast<long long>(gridDim.x) * kSegs;
-  for (long long first = static_cast<long long>(blockIdx.x) * kSegs; first < a.B; first += stride) {
-    const long long prob = first + seg;
-    bool active = false;
-    if (prob < a.B) active = step_problem<W, E>(a, prob, prob, sl, rho_lds[seg], alpha_lds[seg]);
-    active_count += __builtin_popcountll(__builtin_amdgcn_ballot_w64(active && sl == 0));
-  }
-  if (lane == 0 && active_count != 0) atomicAdd(a.active, active_count);
+// static LDS of a step kernel, per segment: 1 / (s.y) per ring slot and the alpha of the running recursion
+constexpr int kRhoLds = MI355_LBFGS_MAX_M, kAlphaLds = MI355_LBFGS_MAX_M + 1;
+template <int W>
+constexpr int step_lds_bytes() {
+  return (kWave / W) * (kRhoLds + kAlphaLds) * static_cast<int>(sizeof(double));
 }
 
-// The same step on a compacted handle (a kernel of its own: step_kernel stays as it was built before there were lists):
-// slot s of x_eval / f / g belongs to problem ids[s], ids ascending.  a.B is the LENGTH OF THE LIST here (nothing of a
-// step is indexed by the batch size), and the grid is sized from it.
-template <int W, int E>
-__global__ __launch_bounds__(64) void listed_step_kernel(const Args a, const long long* ids) {
+// One step of every row a.B counts, and the tally of the problems still active after it.  Dense (kListed false): row
+// r is problem r and a.B the batch.  Listed: row s of x_eval / f / g belongs to problem ids[s], ids ascending, a.B is
+// the LENGTH OF THE LIST (nothing of a step is indexed by the batch size) and the grid is sized from it.  (Why the grid
+// loop is spelled here and not in a function the three paths share: run_steps of lbfgsb_ask_tell_kernel.hpp.)
+template <int W, int E, bool kListed>
+__device__ __forceinline__ void run_steps(const Args a, const long long* ids) {
   constexpr int kSegs = kWave / W;
-  __shared__ double rho_lds[kSegs][MI355_LBFGS_MAX_M];
-  __shared__ double alpha_lds[kSegs][MI355_LBFGS_MAX_M + 1];
+  __shared__ double rho_lds[kSegs][kRhoLds];
+  __shared__ double alpha_lds[kSegs][kAlphaLds];
+  static_assert(sizeof(rho_lds) + sizeof(alpha_lds) == step_lds_bytes<W>(), "what the launch reports");
   const int lane = threadIdx.x;
   const int seg = lane / W;
   const int sl = lane % W;
@@ -442,10 +359,21 @@ __global__ __launch_bounds__(64) void listed_step_kernel(const Args a, const lon
   for (long long first = static_cast<long long>(blockIdx.x) * kSegs; first < a.B; first += stride) {
     const long long slot = first + seg;
     bool active = false;
-    if (slot < a.B) active = step_problem<W, E>(a, ids[slot], slot, sl, rho_lds[seg], alpha_lds[seg]);
+    if (slot < a.B) active = step_problem<W, E>(a, kListed ? ids[slot] : slot, slot, sl, rho_lds[seg], alpha_lds[seg]);
     active_count += __builtin_popcountll(__builtin_amdgcn_ballot_w64(active && sl == 0));
   }
   if (lane == 0 && active_count != 0) atomicAdd(a.active, active_count);
+}
+
+// The two entry points of run_steps: two kernels, so that the dense one takes no list argument and tests none.
+template <int W, int E>
+__global__ __launch_bounds__(64) void step_kernel(const Args a) {
+  run_steps<W, E, false>(a, nullptr);
+}
+
+template <int W, int E>
+__global__ __launch_bounds__(64) void listed_step_kernel(const Args a, const long long* ids) {
+  run_steps<W, E, true>(a, ids);
 }
 
 // (the state initialisation and the result gather are ask_tell_kernel_common.hpp's)

@@ -6,8 +6,9 @@
 // OptimizationStep :141-238, GetGeneralizedCauchyPoint :318-430, SubspaceMinimization / FindAlpha :459-515 / :435-457,
 // MoreThuente::cvsrch linesearch/more_thuente.h:137-256, Progress::Update solver/progress.h:153-327), cut at its FIVE
 // objective evaluations.  The statements are those of lbfgsb_solve_kernel<E, Obj, M, MI355_LS_MORE_THUENTE, NoOuterLoop,
-// 16, OwnBox> and of mt_cvsrch on the same operands in the same order (its free primitives are used as they are), so a
-// callback that evaluates with the library's own functor reproduces the persistent reference-order kernel bit for bit.
+// 16, OwnBox> and of mt_cvsrch on the same operands in the same order (its free primitives are used as they are; the
+// search cut at its evaluation is MtSearch<double> of more_thuente_resume.hpp), so a callback that evaluates with the
+// library's own functor reproduces the persistent reference-order kernel bit for bit.
 //
 // Mapping: one problem per 16-lane segment (one DPP row), lane sl owns coordinates sl * E + e and row sl of the 2k x 2k
 // algebra; a workgroup is one wavefront; the grid strides over the batch.  The box is read through a row stride (0: one
@@ -28,6 +29,7 @@
 #pragma once
 #include "lbfgsb_ask_tell_config.hpp"
 #include "lbfgsb_kernel.hpp"
+#include "more_thuente_resume.hpp"
 #include "ask_tell_kernel_common.hpp"
 
 namespace mi355 {
@@ -45,9 +47,6 @@ __device__ __forceinline__ int step_problem(const Args& a, long long prob, long 
   constexpr int K2 = 2 * M;
   static_assert(K2 <= W, "the 2M rows of the compact representation must fit the lanes of one segment");
   constexpr double kMax = 1.7976931348623157e308;
-  // more_thuente.h:140-147
-  constexpr double xtol = 1e-15, ftol = 1e-4, gtol = 0.9, stpmin = 1e-15, stpmax = 1e15, xtrapf = 4.0;
-  constexpr int maxfev = 20;
 
   Scalars* const sc = a.scalars + prob;
   const int phase = sc->phase;
@@ -132,11 +131,7 @@ __device__ __forceinline__ int step_problem(const Args& a, long long prob, long 
 #pragma unroll
   for (int j = 0; j < K2; ++j) mm_row[j] = 0.0;
 
-  // the search's scalars (mt_cvsrch), segment-uniform
-  double stx = 0.0, fx = 0.0, dgx = 0.0, sty = 0.0, fy = 0.0, dgy = 0.0, stp = 0.0;
-  double width = 0.0, width1 = 0.0, finit = 0.0, dginit = 0.0, stmin = 0.0, stmax = 0.0;
-  bool brackt = false, stage1 = true;
-  int infoc = 1, ls_nfev = 0;
+  MtSearch<double> mt;  // the running search, segment-uniform
 
   // everything but the search's scalars; f_store: the value at X (the returned f once finished)
   auto store_scalars = [&](int next_phase, double f_store) {
@@ -150,32 +145,13 @@ __device__ __forceinline__ int step_problem(const Args& a, long long prob, long 
       sc->phase = next_phase;
     }
   };
-  // more_thuente.h:179-195: the interval, the clamp and the fallback before an evaluation
-  auto before_evaluation = [&]() {
-    if (brackt) {
-      stmin = dmin(stx, sty);
-      stmax = dmax(stx, sty);
-    } else {
-      stmin = stx;
-      stmax = stp + xtrapf * (stp - stx);
-    }
-    stp = dclamp(stp, stpmin, stpmax);
-    if ((brackt && ((stp <= stmin) || (stp >= stmax))) || (ls_nfev >= maxfev - 1) || (infoc == 0) ||
-        (brackt && ((stmax - stmin) <= (xtol * stmax)))) {
-      stp = stx;
-    }
-  };
   // the trial point wa + stp s = wa - stp d into the evaluation buffer, and the search's scalars
   auto ask_trial = [&](const double (&wa)[E], const double (&d)[E]) {
 #pragma unroll
     for (int e = 0; e < E; ++e)
-      if (sl * E + e < n) a.x_eval[cbase + e] = AR::nmadd(stp, d[e], wa[e]);
+      if (sl * E + e < n) a.x_eval[cbase + e] = AR::nmadd(mt.stp, d[e], wa[e]);
     if (sl == 0) {
-      sc->stx = stx; sc->fx = fx; sc->dgx = dgx;
-      sc->sty = sty; sc->fy = fy; sc->dgy = dgy;
-      sc->stp = stp; sc->width = width; sc->width1 = width1;
-      sc->finit = finit; sc->dginit = dginit; sc->stmin = stmin; sc->stmax = stmax;
-      sc->brackt = brackt; sc->stage1 = stage1; sc->infoc = infoc; sc->ls_nfev = ls_nfev;
+      mt.store(sc);
       sc->nfev = nfev;
       sc->phase = kPhaseTrial;
     }
@@ -218,53 +194,15 @@ __device__ __forceinline__ int step_problem(const Args& a, long long prob, long 
         load_vec(Dr, d);
         load_caller_g(gn);
         const double fn = a.f[slot];
-        stx = sc->stx; fx = sc->fx; dgx = sc->dgx;
-        sty = sc->sty; fy = sc->fy; dgy = sc->dgy;
-        stp = sc->stp; width = sc->width; width1 = sc->width1;
-        finit = sc->finit; dginit = sc->dginit; stmin = sc->stmin; stmax = sc->stmax;
-        brackt = sc->brackt != 0; stage1 = sc->stage1 != 0; infoc = sc->infoc; ls_nfev = sc->ls_nfev;
-        const double dgtest = ftol * dginit;
-        ls_nfev++;
-        nfev++;
-        const double dg = -seg_dot<W, E, AR>(gn, d);  // g.s
-        const double ftest1 = finit + stp * dgtest;
-        int info = 0;
-        if ((brackt & ((stp <= stmin) | (stp >= stmax))) | (infoc == 0)) info = 6;
-        if ((stp == stpmax) & (fn <= ftest1) & (dg <= dgtest)) info = 5;
-        if ((stp == stpmin) & ((fn > ftest1) | (dg >= dgtest))) info = 4;
-        if (ls_nfev >= maxfev) info = 3;
-        if (brackt & (stmax - stmin <= xtol * stmax)) info = 2;
-        if ((fn <= ftest1) & (__builtin_fabs(dg) <= gtol * (-dginit))) info = 1;
-        if (info == 0) {
-          if (stage1 & (fn <= ftest1) & (dg >= dmin(ftol, gtol) * dginit)) stage1 = false;
-          const bool modified = stage1 & (fn <= fx) & (fn > ftest1);
-          StepInterval iv;
-          iv.stx = stx; iv.sty = sty; iv.stp = stp; iv.brackt = brackt; iv.info = infoc; iv.rc = 0;
-          iv.fx = modified ? fx - stx * dgtest : fx;
-          iv.fy = modified ? fy - sty * dgtest : fy;
-          iv.dx = modified ? dgx - dgtest : dgx;
-          iv.dy = modified ? dgy - dgtest : dgy;
-          const double fm = modified ? fn - stp * dgtest : fn;
-          const double dgm = modified ? dg - dgtest : dg;
-          iv = mt_cstep(iv, fm, dgm, stmin, stmax);
-          stx = iv.stx; sty = iv.sty; stp = iv.stp; brackt = iv.brackt; infoc = iv.info;
-          fx = modified ? iv.fx + stx * dgtest : iv.fx;
-          fy = modified ? iv.fy + sty * dgtest : iv.fy;
-          dgx = modified ? iv.dx + dgtest : iv.dx;
-          dgy = modified ? iv.dy + dgtest : iv.dy;
-          if (brackt) {
-            if (__builtin_fabs(sty - stx) >= 0.66 * width1) stp = stx + 0.5 * (sty - stx);
-            width1 = width;
-            width = __builtin_fabs(sty - stx);
-          }
-          before_evaluation();
+        mt.load(sc);
+        if (mt.after_evaluation(fn, [&]() { nfev++; return -seg_dot<W, E, AR>(gn, d); }) == 0) {  // (g.s)
           ask_trial(xcur, d);
           return kAskTrial;
         }
         // the search ended: the accepted point, re-formed from the accepted step (more_thuente_device.hpp:413)
 #pragma unroll
         for (int e = 0; e < E; ++e) {
-          x[e] = AR::nmadd(stp, d[e], xcur[e]);
+          x[e] = AR::nmadd(mt.stp, d[e], xcur[e]);
           g[e] = gn[e];
         }
         f = fn;
@@ -912,7 +850,7 @@ __device__ __forceinline__ int step_problem(const Args& a, long long prob, long 
   double dneg[E];  // negated direction (mt_cvsrch runs along -dneg)
 #pragma unroll
   for (int e = 0; e < E; ++e) dneg[e] = -(smin[e] - x[e]);
-  dginit = -seg_dot<W, E>(g, dneg);
+  const double dginit = -seg_dot<W, E>(g, dneg);
   store_vec(Dr, dneg);
   if (dginit >= 0.0) {  // more_thuente.h:152-156: no evaluation; the next call finishes this iteration
     store_scalars(kPhaseNoEval, f);
@@ -920,70 +858,44 @@ __device__ __forceinline__ int step_problem(const Args& a, long long prob, long 
   }
   // ---- the search starts (more_thuente.h:158-177) and asks for its first trial -----------------------------------------
   store_scalars(kPhaseTrial, f);
-  brackt = false;
-  stage1 = true;
-  infoc = 1;
-  ls_nfev = 0;
-  finit = f;
-  width = stpmax - stpmin;
-  width1 = 2.0 * width;
-  stx = 0.0; fx = finit; dgx = dginit;
-  sty = 0.0; fy = finit; dgy = dginit;
-  stp = 1.0;
-  before_evaluation();
+  mt.start(f, dginit, 1.0);
   ask_trial(x, dneg);
   return kAskTrial;
 }
 
+// dynamic LDS of a step kernel: one segment's layout of lbfgsb_solve_kernel per segment of the wavefront
 template <int E, int M>
-__global__ __launch_bounds__(64) void step_kernel(const Args a) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  constexpr int W = kLanes;
-  constexpr int kSegs = kWave / W;
-  const int lane = threadIdx.x;
-  const int seg = lane / W;
-  const int sl = lane % W;
-  double* const base = lds + seg * lbfgsb_lds_doubles_per_problem<M>(W * E, 0);
-  unsigned long long active_count = 0;  // wavefront-uniform
-  unsigned long long ask_count[kAskKinds - 1] = {0, 0, 0, 0};
-  const long long stride = static_cast<long long>(gridDim.x) * kSegs;
-  for (long long first = static_cast<long long>(blockIdx.x) * kSegs; first < a.B; first += stride) {
-    const long long prob = first + seg;
-    int ask = kNotActive;
-    if (prob < a.B) ask = step_problem<E, M>(a, prob, prob, sl, base);
-    const bool lead = sl == 0;
-    active_count += __builtin_popcountll(__builtin_amdgcn_ballot_w64(lead && ask != kNotActive));
-#pragma unroll
-    for (int kind = 0; kind < kAskKinds - 1; ++kind)
-      ask_count[kind] += __builtin_popcountll(__builtin_amdgcn_ballot_w64(lead && ask == kind));
-  }
-  if (lane == 0) {
-    if (active_count != 0) atomicAdd(a.active, active_count);
-#pragma unroll
-    for (int kind = 0; kind < kAskKinds - 1; ++kind)
-      if (ask_count[kind] != 0) atomicAdd(a.asks + kind, ask_count[kind]);
-  }
+__host__ __device__ inline int segment_lds_doubles() {
+  return lbfgsb_lds_doubles_per_problem<M>(kLanes * E, 0);
+}
+template <int E, int M>
+inline int step_lds_bytes() {
+  return (kWave / kLanes) * segment_lds_doubles<E, M>() * static_cast<int>(sizeof(double));
 }
 
-// The same step on a compacted handle (a kernel of its own: step_kernel stays as it was built before there were lists):
-// slot s of x_eval / f / g belongs to problem ids[s], ids ascending.  a.B is the LENGTH OF THE LIST here (nothing of a
-// step is indexed by the batch size), and the grid is sized from it.
-template <int E, int M>
-__global__ __launch_bounds__(64) void listed_step_kernel(const Args a, const long long* ids) {
+// One step of every row a.B counts, the tally of the problems still active after it and of what they ask for.  Dense
+// (kListed false): row r is problem r and a.B the batch.  Listed: row s of x_eval / f / g belongs to problem ids[s],
+// ids ascending, a.B is the LENGTH OF THE LIST (nothing of a step is indexed by the batch size) and the grid is sized
+// from it.  The grid loop is spelled here, as in the run_steps of the two Lbfgs paths, and Args comes by value: handed to
+// a shared function as a callback that tallies through captured references, the loop cost the kernels at two and four
+// coordinates per lane 8 to 26 registers; as a shared loop object, two in the listed kernels; Args by reference, two in
+// step_kernel<4, 5> (profiles/ask_tell_box_kernel_resources.txt).
+template <int E, int M, bool kListed>
+__device__ __forceinline__ void run_steps(const Args a, const long long* ids) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   constexpr int W = kLanes;
   constexpr int kSegs = kWave / W;
   const int lane = threadIdx.x;
   const int seg = lane / W;
   const int sl = lane % W;
-  double* const base = lds + seg * lbfgsb_lds_doubles_per_problem<M>(W * E, 0);
+  double* const base = lds + seg * segment_lds_doubles<E, M>();
   unsigned long long active_count = 0;  // wavefront-uniform
   unsigned long long ask_count[kAskKinds - 1] = {0, 0, 0, 0};
   const long long stride = static_cast<long long>(gridDim.x) * kSegs;
   for (long long first = static_cast<long long>(blockIdx.x) * kSegs; first < a.B; first += stride) {
     const long long slot = first + seg;
     int ask = kNotActive;
-    if (slot < a.B) ask = step_problem<E, M>(a, ids[slot], slot, sl, base);
+    if (slot < a.B) ask = step_problem<E, M>(a, kListed ? ids[slot] : slot, slot, sl, base);
     const bool lead = sl == 0;
     active_count += __builtin_popcountll(__builtin_amdgcn_ballot_w64(lead && ask != kNotActive));
 #pragma unroll
@@ -998,37 +910,18 @@ __global__ __launch_bounds__(64) void listed_step_kernel(const Args a, const lon
   }
 }
 
-// x0 into the evaluation buffer and into vector X of the state row (whose padding and scalars the host has zeroed: phase
-// "first evaluation pending"), so that results() before the first step returns the start point; the caller's box — or
-// the reference's default one — into the handle's copy, with a flag raised for a NaN bound.  (Not a template: it is
-// defined in one unit only, dispatch_lbfgsb_ask_tell.hip; the unit of the listed step kernels leaves it out.)
-#ifndef MI355_ASK_TELL_LISTED_TU
-__global__ void init_kernel(const InitArgs a) {
-  const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t >= a.B * a.n) return;
-  const long long b = t / a.n;
-  const int j = static_cast<int>(t - b * a.n);
-  const double v = a.x0[t];
-  a.x_eval[t] = v;
-  a.vectors[b * a.row + j] = v;
-  if (j == 0) a.scalars[b].status = MI355_STATUS_NOT_STARTED;
-  if (t == 0) a.asks[kAskFirst] = static_cast<unsigned long long>(a.B);
-  const bool rows = a.box_stride_in != 0;
-  if (rows || b == 0) {
-    double lo = -1.7976931348623157e308, hi = 1.7976931348623157e308;  // lowest() .. max() (lbfgsb.h:124-129)
-    if (a.lower_in != nullptr) {
-      lo = a.lower_in[b * a.box_stride_in + j];
-      hi = a.upper_in[b * a.box_stride_in + j];
-    }
-    if (lo != lo || hi != hi) *a.nan_flag = 1;
-    const long long at = rows ? t : j;
-    a.lower[at] = lo;
-    a.upper[at] = hi;
-  }
+// The two entry points of run_steps: two kernels, so that the dense one takes no list argument and tests none.
+template <int E, int M>
+__global__ __launch_bounds__(64) void step_kernel(const Args a) {
+  run_steps<E, M, false>(a, nullptr);
 }
-#endif
 
-// (the result gather is ask_tell_kernel_common.hpp's)
+template <int E, int M>
+__global__ __launch_bounds__(64) void listed_step_kernel(const Args a, const long long* ids) {
+  run_steps<E, M, true>(a, ids);
+}
+
+// (the state initialisation is dispatch_lbfgsb_ask_tell.hip's, the result gather ask_tell_kernel_common.hpp's)
 
 }  // namespace ask_tell_box
 }  // namespace mi355

@@ -1,8 +1,9 @@
 """The listed mode of the ask/tell handles (mi355_ask_tell_compact_*, mi355_ask_tell_ids_*) without a GPU: its six
 symbols are declared, exported and listed with argtypes; null arguments are argument errors and crash nothing; the header
 test program compiles with plain g++ with and without exceptions; and, from the code-object metadata of a gfx950
-cross-compile, the compaction kernels and the listed step kernels run without scratch or spilled vector registers while
-the unlisted step kernels keep the register counts of profiles/ask_tell_kernel_resources.txt."""
+cross-compile, the compaction kernels and the step kernels of the three paths, listed and unlisted, run without scratch or
+spilled vector registers while the unlisted fp64 step kernels keep the register counts of
+profiles/ask_tell_kernel_resources.txt."""
 import ctypes as C
 import os
 import re
@@ -68,7 +69,9 @@ def test_header_program_compiles(flags):
 UNITS = {
     "dispatch_lbfgs_ask_tell": {"ask_tell::step_kernel": 6},
     "dispatch_lbfgs_ask_tell_listed": {"ask_tell::listed_step_kernel": 6},
+    "dispatch_lbfgs_ask_tell_f32": {"ask_tell_f32::step_kernel": 6},
     "dispatch_lbfgs_ask_tell_f32_listed": {"ask_tell_f32::listed_step_kernel": 6},
+    "dispatch_lbfgsb_ask_tell": {"ask_tell_box::step_kernel": 6},
     "dispatch_lbfgsb_ask_tell_listed": {"ask_tell_box::listed_step_kernel": 6},
     "dispatch_ask_tell_compact": {"ask_tell_compact::count_kernel": 3, "ask_tell_compact::scan_kernel": 1,
                                   "ask_tell_compact::scatter_kernel": 3},
@@ -118,7 +121,7 @@ def test_unlisted_step_kernels_keep_their_registers(compiled):
     """the figures of profiles/ask_tell_kernel_resources.txt, read from that file"""
     text = open(os.path.join(REPO, "profiles", "ask_tell_kernel_resources.txt")).read()
     want = {(int(w), int(e)): int(v) for w, e, v in re.findall(r"ask_tell::step_kernel<(\d+), (\d+)>\s+(\d+)\s", text)}
-    assert want == {(8, 1): 126, (16, 1): 126, (32, 1): 126, (64, 1): 125, (64, 2): 136, (64, 4): 156}
+    assert want == {(8, 1): 124, (16, 1): 124, (32, 1): 124, (64, 1): 123, (64, 2): 134, (64, 4): 154}
     rows = _of(compiled["dispatch_lbfgs_ask_tell"], "ask_tell::step_kernel")
     assert len(rows) == 6, sorted(compiled["dispatch_lbfgs_ask_tell"])
     got = {}
