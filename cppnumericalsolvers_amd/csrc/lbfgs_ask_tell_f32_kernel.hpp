@@ -3,8 +3,8 @@
 // next objective evaluation, and the CALLER evaluates the batch of float trial points and hands float f, g back.
 //
 // The phase machine is that of lbfgs_ask_tell_kernel.hpp; the STATEMENTS are those of lbfgs_f32_kernel.hpp and of the
-// float mt_cvsrch / mt_cstep (more_thuente_f32_device.hpp; the search cut at its evaluation is MtSearch<float> of
-// more_thuente_resume.hpp) on the same operands in the same order, cut at the objective evaluation, so a callback that
+// float mt_cvsrch / mt_cstep (more_thuente_device.hpp; the search cut at its evaluation is MtSearch<float> of the same
+// header) on the same operands in the same order, cut at the objective evaluation, so a callback that
 // evaluates with the library's own float functor reproduces the persistent float kernel bit for bit.  What that means
 // against the fp64 ask/tell kernel:
 //   * s.y is stored per ring slot, not 1 / (s.y); the |s.y| < eps skip is a real skip and rho = one / denom is formed
@@ -30,7 +30,6 @@
 
 #include "lbfgs_ask_tell_f32_config.hpp"
 #include "lbfgs_f32_kernel.hpp"
-#include "more_thuente_resume.hpp"
 #include "wave_primitives_f32.hpp"
 #include "ask_tell_kernel_common.hpp"
 
@@ -149,7 +148,7 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, long
         ask_trial();
         return true;
       }
-      // the search ended: the accepted point, re-formed from the accepted step (more_thuente_f32_device.hpp:248)
+      // the search ended: the accepted point, re-formed from the accepted step (as f32::mt_cvsrch ends)
 #pragma unroll
       for (int e = 0; e < E; ++e) x[e] = xp[e] - mt.stp * d[e];
     } else {

@@ -5,8 +5,8 @@
 // Device counterpart of the same reference code as lbfgs_kernel.hpp (Solver::Minimize solver/solver.h:181-224,
 // Lbfgs::OptimizationStep solver/lbfgs.h:89-303, MoreThuente::cvsrch linesearch/more_thuente.h:137-256,
 // Progress::Update solver/progress.h:153-327), cut at the objective evaluation: the statements are those of
-// lbfgs_kernel.hpp and mt_cvsrch (more_thuente_device.hpp; the search cut at its evaluation is MtSearch<double> of
-// more_thuente_resume.hpp) on the same operands in the same order, so a callback that evaluates with the library's own
+// lbfgs_kernel.hpp and mt_cvsrch (more_thuente_device.hpp; the search cut at its evaluation is MtSearch<double> of the
+// same header) on the same operands in the same order, so a callback that evaluates with the library's own
 // functor reproduces the persistent exact kernel bit for bit.
 //
 // Mapping: one problem per segment of W lanes, lane sl owns coordinates sl * E + e; every reduction is a segment
@@ -25,7 +25,7 @@
 // No loop depends on a stopping test firing: the two-loop recursion runs mem_count <= m trips.
 #pragma once
 #include "lbfgs_ask_tell_config.hpp"
-#include "more_thuente_resume.hpp"
+#include "more_thuente_device.hpp"
 #include "progress_device.hpp"
 #include "wave_primitives.hpp"
 #include "ask_tell_kernel_common.hpp"
@@ -138,7 +138,7 @@ __device__ __forceinline__ bool step_problem(const Args& a, long long prob, long
         ask_trial();
         return true;
       }
-      // the search ended: the accepted point, re-formed from the accepted step (more_thuente_device.hpp:413)
+      // the search ended: the accepted point, re-formed from the accepted step (as mt_cvsrch ends)
 #pragma unroll
       for (int e = 0; e < E; ++e) xn[e] = AR::nmadd(mt.stp, d[e], x[e]);
     } else {

@@ -6,7 +6,7 @@
 //   Lbfgs::OptimizationStep     solver/lbfgs.h:89-303     (two-loop recursion, descent check and fallback, alpha_init,
 //                                                          line search, pair test, ring push, gamma update)
 //   Progress::Update            solver/progress.h:153-327 (every threshold of the stop record converted to float once)
-// with cvsrch / cstep from more_thuente_f32_device.hpp.  A file of its own: the fp64 kernels (lbfgs_kernel.hpp) are not
+// with f32::mt_cvsrch / mt_cstep<float> from more_thuente_device.hpp.  A file of its own: the fp64 kernels (lbfgs_kernel.hpp) are not
 // templated on a scalar type and their object code does not change.
 //
 // Mapping.  One problem per segment of W lanes, E coordinates per lane, coordinate j = sl * E + e; padding coordinates
@@ -32,7 +32,7 @@
 #include "../../include/mi355_lbfgs.h"
 #include "lbfgs_f32_config.hpp"
 #include "lbfgs_kernel.hpp"
-#include "more_thuente_f32_device.hpp"
+#include "more_thuente_device.hpp"
 #include "objectives_f32.hpp"
 #include "solver_driver.hpp"
 #include "wave_primitives_f32.hpp"

@@ -455,76 +455,23 @@ __global__ __launch_bounds__(T) void lbfgs_wide_kernel(const WideArgs a) {
           f_next = f;
         }
       } else {   // MoreThuente (more_thuente.h:120-256)
-        double stp = alpha_init;
-        int info = 0, infoc = 1;
-        constexpr double xtol = 1e-15, ftol = 1e-4, gtol = 0.9, stpmin = 1e-15, stpmax = 1e15, xtrapf = 4.0;
-        constexpr int maxfev = 20;
-        int ls_nfev = 0;
         if (dginit >= 0.0) {  // :152-156: nothing evaluated, next = current
           wide_for<E>(n, [&](int j, int e) {
             xn.at(j, e) = xc.get(j, e);
             gn.at(j, e) = gc.get(j, e);
           });
         } else {
-          bool brackt = false, stage1 = true;
-          const double finit = f;
-          const double dgtest = ftol * dginit;
-          double width = stpmax - stpmin;
-          double width1 = 2.0 * width;
-          double stx = 0.0, fx = finit, dgx = dginit;
-          double sty = 0.0, fy = finit, dgy = dginit;
-          double stmin, stmax;
-          while (true) {
-            if (brackt) {
-              stmin = dmin(stx, sty);
-              stmax = dmax(stx, sty);
-            } else {
-              stmin = stx;
-              stmax = stp + xtrapf * (stp - stx);
-            }
-            stp = dclamp(stp, stpmin, stpmax);
-            if ((brackt && ((stp <= stmin) || (stp >= stmax))) || (ls_nfev >= maxfev - 1) || (infoc == 0) ||
-                (brackt && ((stmax - stmin) <= (xtol * stmax)))) {
-              stp = stx;
-            }
+          MtSearch<double> mt;
+          mt.start(f, dginit, alpha_init);
+          double gdn;  // g . d at the trial point, from the objective's own pass
+          do {
+            const double stp = mt.stp;
             if constexpr (E == 0) __syncthreads();  // every reader of the previous trial point is done
             wide_for<E>(n, [&](int j, int e) { xn.at(j, e) = stp * (-d.get(j, e)) + xc.get(j, e); });   // wa + stp * s
-            double gdn;
             f_next = obj.template eval<E>(xn, gn, n, red, xmem, &d, &gdn);
-            ls_nfev++;
-            const double dg = -gdn;                                                          // g . s
-            const double ftest1 = finit + stp * dgtest;
-            if ((brackt & ((stp <= stmin) | (stp >= stmax))) | (infoc == 0)) info = 6;
-            if ((stp == stpmax) & (f_next <= ftest1) & (dg <= dgtest)) info = 5;
-            if ((stp == stpmin) & ((f_next > ftest1) | (dg >= dgtest))) info = 4;
-            if (ls_nfev >= maxfev) info = 3;
-            if (brackt & (stmax - stmin <= xtol * stmax)) info = 2;
-            if ((f_next <= ftest1) & (__builtin_fabs(dg) <= gtol * (-dginit))) info = 1;
-            if (info != 0) break;
-            if (stage1 & (f_next <= ftest1) & (dg >= dmin(ftol, gtol) * dginit)) stage1 = false;
-            const bool modified = stage1 & (f_next <= fx) & (f_next > ftest1);
-            StepInterval iv;
-            iv.stx = stx; iv.sty = sty; iv.stp = stp; iv.brackt = brackt; iv.info = infoc; iv.rc = 0;
-            iv.fx = modified ? fx - stx * dgtest : fx;
-            iv.fy = modified ? fy - sty * dgtest : fy;
-            iv.dx = modified ? dgx - dgtest : dgx;
-            iv.dy = modified ? dgy - dgtest : dgy;
-            const double fm = modified ? f_next - stp * dgtest : f_next;
-            const double dgm = modified ? dg - dgtest : dg;
-            iv = mt_cstep(iv, fm, dgm, stmin, stmax);
-            stx = iv.stx; sty = iv.sty; stp = iv.stp; brackt = iv.brackt; infoc = iv.info;
-            fx = modified ? iv.fx + stx * dgtest : iv.fx;
-            fy = modified ? iv.fy + sty * dgtest : iv.fy;
-            dgx = modified ? iv.dx + dgtest : iv.dx;
-            dgy = modified ? iv.dy + dgtest : iv.dy;
-            if (brackt) {
-              if (__builtin_fabs(sty - stx) >= 0.66 * width1) stp = stx + 0.5 * (sty - stx);
-              width1 = width;
-              width = __builtin_fabs(sty - stx);
-            }
-          }
+          } while (mt.after_evaluation(f_next, [&] { return -gdn; }) == 0);                  // g . s
+          nfev += static_cast<unsigned>(mt.ls_nfev);
         }
-        nfev += static_cast<unsigned>(ls_nfev);
       }
 
       // ---- :239-298 and the norms of Progress::Update (progress.h:188-195), one pass ----------------------------------

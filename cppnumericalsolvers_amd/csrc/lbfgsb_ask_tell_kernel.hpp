@@ -7,7 +7,7 @@
 // MoreThuente::cvsrch linesearch/more_thuente.h:137-256, Progress::Update solver/progress.h:153-327), cut at its FIVE
 // objective evaluations.  The statements are those of lbfgsb_solve_kernel<E, Obj, M, MI355_LS_MORE_THUENTE, NoOuterLoop,
 // 16, OwnBox> and of mt_cvsrch on the same operands in the same order (its free primitives are used as they are; the
-// search cut at its evaluation is MtSearch<double> of more_thuente_resume.hpp), so a callback that evaluates with the
+// search cut at its evaluation is MtSearch<double> of more_thuente_device.hpp), so a callback that evaluates with the
 // library's own functor reproduces the persistent reference-order kernel bit for bit.
 //
 // Mapping: one problem per 16-lane segment (one DPP row), lane sl owns coordinates sl * E + e and row sl of the 2k x 2k
@@ -29,7 +29,6 @@
 #pragma once
 #include "lbfgsb_ask_tell_config.hpp"
 #include "lbfgsb_kernel.hpp"
-#include "more_thuente_resume.hpp"
 #include "ask_tell_kernel_common.hpp"
 
 namespace mi355 {
@@ -199,7 +198,7 @@ __device__ __forceinline__ int step_problem(const Args& a, long long prob, long 
           ask_trial(xcur, d);
           return kAskTrial;
         }
-        // the search ended: the accepted point, re-formed from the accepted step (more_thuente_device.hpp:413)
+        // the search ended: the accepted point, re-formed from the accepted step (as mt_cvsrch ends)
 #pragma unroll
         for (int e = 0; e < E; ++e) {
           x[e] = AR::nmadd(mt.stp, d[e], xcur[e]);

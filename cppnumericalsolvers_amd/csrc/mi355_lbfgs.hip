@@ -384,7 +384,7 @@ __global__ void cstep_kernel(long long count, double* rec, int* ret) {
   const long long t = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x;
   if (t >= count) return;
   double* r = rec + t * 13;
-  StepInterval iv;
+  MtInterval<double> iv;
   iv.stx = r[0]; iv.fx = r[1]; iv.dx = r[2]; iv.sty = r[3]; iv.fy = r[4]; iv.dy = r[5]; iv.stp = r[6];
   const double fp = r[7], dp = r[8];
   iv.brackt = r[9] != 0.0;

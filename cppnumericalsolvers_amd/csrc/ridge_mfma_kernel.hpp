@@ -132,31 +132,9 @@ __global__ __launch_bounds__((kWave / W) == 2 ? 512 : 256) void ridge_mfma_solve
   int past_pos = 0;
   double xinf_bound = 0.0;
   const double n_as_double = static_cast<double>(n);
-  // Moré–Thuente state (more_thuente.h:137-256) between evaluations
-  constexpr double xtol = 1e-15, ftol = 1e-4, gtol = 0.9, stpmin = 1e-15, stpmax = 1e15, xtrapf = 4.0;
-  constexpr int maxfev = 20;
-  double stx = 0, fx = 0, dgx = 0, sty = 0, fy = 0, dgy = 0, stp = 0, stmin = 0, stmax = 0;
-  double width = 0, width1 = 0, finit = 0, dginit = 0, dgtest = 0;
-  bool brackt = false, stage1 = true;
-  int ls_nfev = 0, infoc = 1;
+  MtSearch<double> mt{};  // the running search (more_thuente.h:137-256) between evaluations, segment-uniform
 #pragma unroll
   for (int e = 0; e < E; ++e) x[e] = g[e] = d[e] = wa[e] = gp[e] = 0.0;
-
-  // cvsrch loop head (:179-193): interval bounds, clamp, fall back to the best step
-  auto ls_prepare = [&]() {
-    if (brackt) {
-      stmin = dmin(stx, sty);
-      stmax = dmax(stx, sty);
-    } else {
-      stmin = stx;
-      stmax = stp + xtrapf * (stp - stx);
-    }
-    stp = dclamp(stp, stpmin, stpmax);
-    if ((brackt && ((stp <= stmin) || (stp >= stmax))) || (ls_nfev >= maxfev - 1) || (infoc == 0) ||
-        (brackt && ((stmax - stmin) <= (xtol * stmax)))) {
-      stp = stx;
-    }
-  };
 
 #ifdef MI355_LBFGS_PHASE_TIMING
   unsigned long long lphase_cycles[8];
@@ -203,7 +181,7 @@ __global__ __launch_bounds__((kWave / W) == 2 ? 512 : 256) void ridge_mfma_solve
     // phase instead of being kept in registers across it)
     auto trial_point = [&](double (&xt)[E]) {
 #pragma unroll
-      for (int e = 0; e < E; ++e) xt[e] = !has_problem ? 0.0 : (fresh ? x[e] : AR::nmadd(stp, d[e], wa[e]));
+      for (int e = 0; e < E; ++e) xt[e] = !has_problem ? 0.0 : (fresh ? x[e] : AR::nmadd(mt.stp, d[e], wa[e]));
     };
     {
       double xt[E];
@@ -340,45 +318,11 @@ __global__ __launch_bounds__((kWave / W) == 2 ? 512 : 256) void ridge_mfma_solve
       start_iteration = true;
     } else {
       // ---- cvsrch after an evaluation (:196-252) --------------------------------------------------
-      ls_nfev++;
-      const double dg = -seg_dot<W, E, AR>(g, d);  // g.s
-      const double ftest1 = finit + stp * dgtest;
-      int info = 0;
-      if ((brackt & ((stp <= stmin) | (stp >= stmax))) | (infoc == 0)) info = 6;
-      if ((stp == stpmax) & (f <= ftest1) & (dg <= dgtest)) info = 5;
-      if ((stp == stpmin) & ((f > ftest1) | (dg >= dgtest))) info = 4;
-      if (ls_nfev >= maxfev) info = 3;
-      if (brackt & (stmax - stmin <= xtol * stmax)) info = 2;
-      if ((f <= ftest1) & (__builtin_fabs(dg) <= gtol * (-dginit))) info = 1;
-      if (info == 0) {
-        if (stage1 & (f <= ftest1) & (dg >= dmin(ftol, gtol) * dginit)) stage1 = false;
-        const bool modified = stage1 & (f <= fx) & (f > ftest1);
-        StepInterval iv;
-        iv.stx = stx; iv.sty = sty; iv.stp = stp; iv.brackt = brackt; iv.info = infoc; iv.rc = 0;
-        iv.fx = modified ? fx - stx * dgtest : fx;
-        iv.fy = modified ? fy - sty * dgtest : fy;
-        iv.dx = modified ? dgx - dgtest : dgx;
-        iv.dy = modified ? dgy - dgtest : dgy;
-        const double fm = modified ? f - stp * dgtest : f;
-        const double dgm = modified ? dg - dgtest : dg;
-        iv = mt_cstep(iv, fm, dgm, stmin, stmax);
-        stx = iv.stx; sty = iv.sty; stp = iv.stp; brackt = iv.brackt; infoc = iv.info;
-        fx = modified ? iv.fx + stx * dgtest : iv.fx;
-        fy = modified ? iv.fy + sty * dgtest : iv.fy;
-        dgx = modified ? iv.dx + dgtest : iv.dx;
-        dgy = modified ? iv.dy + dgtest : iv.dy;
-        if (brackt) {
-          if (__builtin_fabs(sty - stx) >= 0.66 * width1) stp = stx + 0.5 * (sty - stx);
-          width1 = width;
-          width = __builtin_fabs(sty - stx);
-        }
-        ls_prepare();
-        continue;  // next pass evaluates wa - stp * d
-      }
+      if (mt.after_evaluation(f, [&] { return -seg_dot<W, E, AR>(g, d); }) == 0) continue;  // (g.s) next pass: wa - stp * d
       // line search finished: the accepted point is the one just evaluated
-      nfev += static_cast<unsigned>(ls_nfev);
+      nfev += static_cast<unsigned>(mt.ls_nfev);
 #pragma unroll
-      for (int e = 0; e < E; ++e) x[e] = AR::nmadd(stp, d[e], wa[e]);
+      for (int e = 0; e < E; ++e) x[e] = AR::nmadd(mt.stp, d[e], wa[e]);
     }
 
     MI355_LPHASE(6);  // end of iteration (update, stopping tests, results) + two-loop + search set-up
@@ -595,7 +539,7 @@ __global__ __launch_bounds__((kWave / W) == 2 ? 512 : 256) void ridge_mfma_solve
         }
       }
       const double descent_direction = -seg_dot<W, E, AR>(g, d);  // :199
-      dginit = descent_direction;                              // = g.s with s = -d, bit for bit
+      double dginit = descent_direction;                       // = g.s with s = -d, bit for bit
       double alpha_init = 1.0;                                 // :207-213
       if (mem_count == 0) {
         const double dn = __builtin_sqrt(seg_dot<W, E, AR>(d, d));
@@ -626,19 +570,7 @@ __global__ __launch_bounds__((kWave / W) == 2 ? 512 : 256) void ridge_mfma_solve
         gp[e] = g[e];
       }
       if (dginit >= 0.0) continue;  // cvsrch :152-156: x, f, g untouched — finish the iteration right away
-      // cvsrch set-up (:158-177)
-      brackt = false;
-      stage1 = true;
-      finit = f;
-      dgtest = ftol * dginit;
-      width = stpmax - stpmin;
-      width1 = 2.0 * width;
-      stx = 0.0; fx = finit; dgx = dginit;
-      sty = 0.0; fy = finit; dgy = dginit;
-      stp = alpha_init;
-      ls_nfev = 0;
-      infoc = 1;
-      ls_prepare();
+      mt.start(f, dginit, alpha_init);  // cvsrch set-up (:158-177) and the first trial step
       break;  // next pass evaluates wa - stp * d
     }
   }

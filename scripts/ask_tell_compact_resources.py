@@ -85,7 +85,7 @@ def main():
     ]
     if before:
         lines.append("before: VGPR / AGPR / instructions of the same kernel in commit %s, where every step kernel spelled the" % args.before_commit)
-        lines.append("More-Thuente search and the grid loop out itself (now MtSearch, csrc/more_thuente_resume.hpp, and run_steps).")
+        lines.append("More-Thuente search and the grid loop out itself (now MtSearch, csrc/more_thuente_device.hpp, and run_steps).")
     lines.append("")
     width = max(len(name) for rows in per_unit.values() for name in rows)
     for unit in UNITS:
