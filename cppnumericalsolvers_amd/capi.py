@@ -60,6 +60,9 @@ EXPORTED_SYMBOLS = [
     "mi355_lbfgs_ask_tell_f32_active", "mi355_lbfgs_ask_tell_f32_results", "mi355_lbfgs_ask_tell_f32_destroy",
     "mi355_lbfgsb_ask_tell_create", "mi355_lbfgsb_ask_tell_x", "mi355_lbfgsb_ask_tell_step", "mi355_lbfgsb_ask_tell_active",
     "mi355_lbfgsb_ask_tell_results", "mi355_lbfgsb_ask_tell_destroy", "mi355_lbfgsb_ask_tell_asks",
+    "mi355_lbfgs_ask_tell_wide_create", "mi355_lbfgs_ask_tell_wide_x", "mi355_lbfgs_ask_tell_wide_step",
+    "mi355_lbfgs_ask_tell_wide_active", "mi355_lbfgs_ask_tell_wide_results", "mi355_lbfgs_ask_tell_wide_destroy",
+    "mi355_lbfgs_ask_tell_wide_compact", "mi355_lbfgs_ask_tell_wide_ids",
 ]
 
 
@@ -287,8 +290,9 @@ def _bind(L):
     L.mi355_lbfgs_minimize_batch_f32.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp, vp]
     L.mi355_lbfgs_minimize_batch_f32_host.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp, vp]
     L.mi355_lbfgs_eval_batch_f32.argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, vp, vp]
-    # the three ask/tell handles share their signatures but for the box arguments of Lbfgsb's create, and its _asks
-    for prefix in ("mi355_lbfgs_ask_tell_", "mi355_lbfgs_ask_tell_f32_", "mi355_lbfgsb_ask_tell_"):
+    # the four ask/tell handles share their signatures but for the box arguments of Lbfgsb's create, and its _asks
+    for prefix in ("mi355_lbfgs_ask_tell_", "mi355_lbfgs_ask_tell_f32_", "mi355_lbfgsb_ask_tell_",
+                   "mi355_lbfgs_ask_tell_wide_"):
         getattr(L, prefix + "create").argtypes = [vp, C.POINTER(Desc), C.c_int64, vp, vp, C.POINTER(vp)]
         getattr(L, prefix + "x").argtypes = [vp, C.POINTER(vp)]
         getattr(L, prefix + "step").argtypes = [vp, vp, vp, C.POINTER(C.c_int64), vp]
@@ -297,6 +301,8 @@ def _bind(L):
         getattr(L, prefix + "destroy").argtypes = [vp]
     L.mi355_lbfgsb_ask_tell_create.argtypes = [vp, C.POINTER(Desc), vp, vp, C.c_int64, C.c_int64, vp, vp, C.POINTER(vp)]
     L.mi355_lbfgsb_ask_tell_asks.argtypes = [vp, C.POINTER(C.c_int64), vp]
+    L.mi355_lbfgs_ask_tell_wide_compact.argtypes = [vp, C.POINTER(C.c_int64), vp]
+    L.mi355_lbfgs_ask_tell_wide_ids.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     for suffix in ASK_TELL_COMPACT_SUFFIXES:
         getattr(L, "mi355_ask_tell_compact_" + suffix).argtypes = [vp, C.POINTER(C.c_int64), vp]
         getattr(L, "mi355_ask_tell_ids_" + suffix).argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]

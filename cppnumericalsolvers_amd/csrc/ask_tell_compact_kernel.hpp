@@ -8,7 +8,7 @@
 //                   other (or several side by side when n is small), with the lanes across the n coordinates
 // No atomic decides a destination: the output is a function of the phase words alone.  Rows move from `rows` to
 // `rows_next`, never in place (the host copies the packed rows back: ask_tell_host.hpp).  Every loop is bounded by the
-// list length, 64 or n.  One file for the three paths: the kernels are templates over the path's Scalars type and its
+// list length, 64 or n.  One file for every path: the kernels are templates over the path's Scalars type and its
 // "finished" phase word.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -41,7 +41,11 @@ __global__ __launch_bounds__(kGroup) void count_kernel(const Args<Scalar, Scalar
 
 // counts[0 .. groups) -> their exclusive scan, counts[groups] = the total.  Thread t owns the groups
 // [t per, (t + 1) per): it sums them, the workgroup scans the kScanThreads sums in LDS, the thread writes its offsets.
+// (A template so that every unit that launches a compaction may hold it: dispatch_ask_tell_compact.hip for the three
+// wavefront paths, dispatch_lbfgs_ask_tell_wide_listed.hip for the path above n = 256.)
+template <int kThreads = kScanThreads>
 __global__ __launch_bounds__(kScanThreads) void scan_kernel(long long* counts, long long groups) {
+  static_assert(kThreads == kScanThreads, "one scan width");
   __shared__ long long sums[kScanThreads];
   const int t = threadIdx.x;
   const long long per = (groups + kScanThreads - 1) / kScanThreads;
@@ -101,7 +105,7 @@ int launch(const Args<Scalar, Scalars>& a, hipStream_t stream) {
   const dim3 grid(static_cast<unsigned>(groups));
   hipLaunchKernelGGL((count_kernel<Scalar, Scalars, kFinished>), grid, dim3(kGroup), 0, stream, a);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, a.counts, groups);
+  hipLaunchKernelGGL(scan_kernel<kScanThreads>, dim3(1), dim3(kScanThreads), 0, stream, a.counts, groups);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL((scatter_kernel<Scalar, Scalars, kFinished>), grid, dim3(kGroup), 0, stream, a, lanes_per_row);
   HIP_TRY(hipGetLastError());

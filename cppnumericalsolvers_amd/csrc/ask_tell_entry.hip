@@ -1,13 +1,15 @@
-// ask_tell_entry.hip — the C entry points of the three ask/tell (reverse communication) paths (include/mi355_lbfgs.h):
-// mi355_lbfgs_ask_tell_* (Lbfgs in double), mi355_lbfgs_ask_tell_f32_* (Lbfgs in float) and mi355_lbfgsb_ask_tell_*
-// (Lbfgsb).  Each path is its traits, its handle struct, its own refusals and its C functions; the rest —
+// ask_tell_entry.hip — the C entry points of the four ask/tell (reverse communication) paths (include/mi355_lbfgs.h):
+// mi355_lbfgs_ask_tell_* (Lbfgs in double), mi355_lbfgs_ask_tell_f32_* (Lbfgs in float), mi355_lbfgsb_ask_tell_*
+// (Lbfgsb) and mi355_lbfgs_ask_tell_wide_* (Lbfgs in double above n = 256, a workgroup per problem).  Each path is its traits, its handle struct, its own refusals and its C functions; the rest —
 // the shared refusals, the one device allocation and its layout, the bodies of the entry points — is ask_tell_host.hpp.
-// The kernels are behind dispatch_lbfgs_ask_tell.hip, dispatch_lbfgs_ask_tell_f32.hip and dispatch_lbfgsb_ask_tell.hip,
-// those of a compacted handle (mi355_ask_tell_compact_*) behind their *_listed.hip twins and dispatch_ask_tell_compact.hip.
+// The kernels are behind dispatch_lbfgs_ask_tell.hip, dispatch_lbfgs_ask_tell_f32.hip, dispatch_lbfgsb_ask_tell.hip and
+// dispatch_lbfgs_ask_tell_wide.hip, those of a compacted handle (mi355_ask_tell_compact_*) behind their *_listed.hip
+// twins and dispatch_ask_tell_compact.hip (the wide path's compaction: its listed unit).
 #include "ask_tell_host.hpp"
 #include "lbfgs_ask_tell_config.hpp"
 #include "lbfgs_ask_tell_f32_config.hpp"
 #include "lbfgsb_ask_tell_config.hpp"
+#include "lbfgs_ask_tell_wide_config.hpp"
 
 using namespace mi355;
 namespace host = mi355::ask_tell_host;
@@ -64,7 +66,34 @@ struct LbfgsbPath {
   static constexpr const char* kWhat = "ask/tell";
 };
 
+// Above n = 256: a workgroup per problem.  The handle's (W, E) hold the padded vector length np at one "coordinate":
+// W * E is what row() and the result gather take as the width of a state vector.
+struct LbfgsWidePath {
+  using Scalar = double;
+  using Scalars = ask_tell_wide::Scalars;
+  using Args = ask_tell_wide::Args;
+  using ResultArgs = ask_tell_wide::ResultArgs;
+  static long long row(int m, int P) { return ask_tell_wide::row_doubles(m, P); }
+  static int step(mi355_lbfgs_ctx* ctx, int, int, const Args& a, hipStream_t stream) {
+    return dispatch_ask_tell_wide_step(ctx, a, stream);
+  }
+  static int listed_step(mi355_lbfgs_ctx* ctx, int, int, const Args& a, const long long* ids, long long listed,
+                         hipStream_t stream) {
+    return dispatch_ask_tell_wide_listed_step(ctx, a, ids, listed, stream);
+  }
+  static constexpr int kFinished = ask_tell_wide::kPhaseFinished;
+  static constexpr auto results = &dispatch_ask_tell_wide_results;
+  static constexpr const char* kPrefix = "Lbfgs ask/tell wide";
+  static constexpr const char* kWhat = "ask/tell wide";
+};
+
 }  // namespace ask_tell_host
+
+// (defined in dispatch_lbfgs_ask_tell_wide_listed.hip)
+template <>
+int dispatch_ask_tell_compact<double, ask_tell_wide::Scalars, ask_tell_wide::kPhaseFinished>(
+    const ask_tell_compact::Args<double, ask_tell_wide::Scalars>& args, hipStream_t stream);
+
 }  // namespace mi355
 
 struct mi355_lbfgs_ask_tell : host::Handle<host::LbfgsPath> {};
@@ -103,7 +132,37 @@ struct mi355_lbfgsb_ask_tell : host::Handle<host::LbfgsbPath> {
   }
 };
 
+struct mi355_lbfgs_ask_tell_wide : host::Handle<host::LbfgsWidePath> {
+  void finish_args(ask_tell_wide::Args& a) const { a.d_in_lds = 0; }  // (the launch decides)
+};
+
 namespace {
+
+// The wide path's refusals around the shared ones, everything before the device is touched
+int check_wide(const mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B) {
+  using T = host::LbfgsWidePath;
+  return host::check_common<T>(
+      ctx, desc, B,
+      [&] {
+        if (desc->n <= MI355_LBFGS_MAX_N)
+          return host::refuse<T>(" is built for n > 256: mi355_lbfgs_ask_tell_create takes n <= 256");
+        if (desc->arithmetic == MI355_ARITH_FMA)
+          return host::refuse<T>(" is built for the exact arithmetic only (no MI355_ARITH_FMA)");
+        if (desc->history_placement == MI355_HISTORY_Y_IN_REGISTERS)
+          return host::refuse<T>(" keeps the history in device memory between calls (no MI355_HISTORY_Y_IN_REGISTERS)");
+        if (desc->hessian_from_functor) return host::refuse<T>(" is built for First-mode functions (no hessian_from_functor)");
+        if (desc->hessian_diagonal != nullptr) return host::refuse<T>(" is built for First-mode functions (no hessian_diagonal)");
+        if (desc->hessian_condition_stop > 0.0)
+          return host::refuse<T>(" is built for First-mode functions (no hessian_condition_stop)");
+        return static_cast<int>(MI355_OK);
+      },
+      [&] {
+        if (desc->lanes_per_problem != 0 || desc->elems_per_lane != 0)
+          return host::refuse<T>(" chooses its own mapping, a workgroup per problem: leave lanes_per_problem and elems_per_lane 0");
+        return static_cast<int>(MI355_OK);
+      },
+      /*allow_wide=*/true);
+}
 
 // Lbfgsb's own refusals around the shared ones, then the box arguments
 int check_box(const mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const double* lower,
@@ -195,6 +254,36 @@ int mi355_lbfgs_ask_tell_results(mi355_lbfgs_ask_tell* handle, double* x_out, do
 }
 int mi355_lbfgs_ask_tell_destroy(mi355_lbfgs_ask_tell* handle) { return host::destroy(handle); }
 
+// ---- Lbfgs in double above n = 256 ------------------------------------------------------------------------------------
+int mi355_lbfgs_ask_tell_wide_create(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const double* x0,
+                                     void* stream, mi355_lbfgs_ask_tell_wide** out) {
+  return host::create(
+      ctx, desc, B, x0, stream, out,
+      [&](mi355_lbfgs_ask_tell_wide& h) {
+        const int rc = check_wide(ctx, desc, B);
+        if (rc != MI355_OK) return rc;
+        h.W = static_cast<int>(ask_tell_wide::padded(desc->n));
+        h.E = 1;
+        return static_cast<int>(MI355_OK);
+      },
+      [&](mi355_lbfgs_ask_tell_wide& h, long long row, hipStream_t s) {
+        return dispatch_ask_tell_wide_init(host::step_args(&h, nullptr, nullptr), x0, row, s);
+      });
+}
+int mi355_lbfgs_ask_tell_wide_x(mi355_lbfgs_ask_tell_wide* handle, const double** x_eval) { return host::x(handle, x_eval); }
+int mi355_lbfgs_ask_tell_wide_step(mi355_lbfgs_ask_tell_wide* handle, const double* f, const double* g,
+                                   int64_t* active_host, void* stream) {
+  return host::step(handle, f, g, active_host, stream);
+}
+int mi355_lbfgs_ask_tell_wide_active(mi355_lbfgs_ask_tell_wide* handle, const int64_t** active_dev) {
+  return host::active(handle, active_dev);
+}
+int mi355_lbfgs_ask_tell_wide_results(mi355_lbfgs_ask_tell_wide* handle, double* x_out, double* f_out, double* g_out,
+                                      mi355_lbfgs_progress* progress_out, void* stream) {
+  return host::results(handle, x_out, f_out, g_out, progress_out, stream);
+}
+int mi355_lbfgs_ask_tell_wide_destroy(mi355_lbfgs_ask_tell_wide* handle) { return host::destroy(handle); }
+
 // ---- Lbfgs in float ---------------------------------------------------------------------------------------------------
 int mi355_lbfgs_ask_tell_f32_create(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const float* x0,
                                     void* stream, mi355_lbfgs_ask_tell_f32** out) {
@@ -261,7 +350,7 @@ int mi355_lbfgsb_ask_tell_results(mi355_lbfgsb_ask_tell* handle, double* x_out, 
 }
 int mi355_lbfgsb_ask_tell_destroy(mi355_lbfgsb_ask_tell* handle) { return host::destroy(handle); }
 
-// ---- the list of the live problems, for the three handle types ----------------------------------------------------------
+// ---- the list of the live problems, for the four handle types ----------------------------------------------------------
 int mi355_ask_tell_compact_lbfgs(mi355_lbfgs_ask_tell* handle, int64_t* listed_host, void* stream) {
   return host::compact(handle, listed_host, stream);
 }
@@ -270,6 +359,12 @@ int mi355_ask_tell_compact_lbfgs_f32(mi355_lbfgs_ask_tell_f32* handle, int64_t* 
 }
 int mi355_ask_tell_compact_lbfgsb(mi355_lbfgsb_ask_tell* handle, int64_t* listed_host, void* stream) {
   return host::compact(handle, listed_host, stream);
+}
+int mi355_lbfgs_ask_tell_wide_compact(mi355_lbfgs_ask_tell_wide* handle, int64_t* listed_host, void* stream) {
+  return host::compact(handle, listed_host, stream);
+}
+int mi355_lbfgs_ask_tell_wide_ids(mi355_lbfgs_ask_tell_wide* handle, const int64_t** ids_dev, int64_t* listed) {
+  return host::ids(handle, ids_dev, listed);
 }
 int mi355_ask_tell_ids_lbfgs(mi355_lbfgs_ask_tell* handle, const int64_t** ids_dev, int64_t* listed) {
   return host::ids(handle, ids_dev, listed);

@@ -1,5 +1,6 @@
-// ask_tell_host.hpp — the host code the three ask/tell (reverse communication) paths share: Lbfgs in double
-// (mi355_lbfgs_ask_tell_*), Lbfgs in float (mi355_lbfgs_ask_tell_f32_*) and Lbfgsb (mi355_lbfgsb_ask_tell_*).  The
+// ask_tell_host.hpp — the host code the four ask/tell (reverse communication) paths share: Lbfgs in double
+// (mi355_lbfgs_ask_tell_*), Lbfgs in float (mi355_lbfgs_ask_tell_f32_*), Lbfgsb (mi355_lbfgsb_ask_tell_*) and Lbfgs in
+// double above n = 256 (mi355_lbfgs_ask_tell_wide_*).  The
 // handle base with its one device allocation, the refusals common to the three, the entry-point bodies
 // (ask_tell_entry.hip turns them into the C functions), the two launches of the dispatch units and their choice among the
 // built mappings.  No kernel lives here.
@@ -43,7 +44,8 @@ struct Args {
 
 }  // namespace ask_tell_compact
 
-// the three launches; instantiated for the three paths in dispatch_ask_tell_compact.hip
+// the three launches; instantiated for the three wavefront paths in dispatch_ask_tell_compact.hip, specialised for the
+// path above n = 256 in dispatch_lbfgs_ask_tell_wide_listed.hip
 template <class Scalar, class Scalars, int kFinished>
 int dispatch_ask_tell_compact(const ask_tell_compact::Args<Scalar, Scalars>& args, hipStream_t stream);
 
@@ -94,8 +96,10 @@ int refuse(const char* text) {
 // (MI355_ERR_UNSUPPORTED, with the reason) — the shared ones here, the path's own in `before` and `after`, which stand
 // where they stood in the path's sequence — then validate()'s argument checks on the fields the path reads (the
 // objective and its parameters are not among them: the caller evaluates).
+// allow_wide: validate()'s range of n ends at MI355_LBFGS_WIDE_MAX_N (the path above n = 256) instead of MI355_LBFGS_MAX_N.
 template <class T, class Before, class After>
-int check_common(const mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, Before before, After after) {
+int check_common(const mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, Before before, After after,
+                 bool allow_wide = false) {
   if (!ctx) return fail(MI355_ERR_INVALID_ARGUMENT, "null context");
   if (!desc) return fail(MI355_ERR_INVALID_ARGUMENT, "null desc");
   if (desc->linesearch == MI355_LS_HAGER_ZHANG)
@@ -112,7 +116,7 @@ int check_common(const mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64
   read.objective_params = nullptr;
   read.n_params = 0;
   read.per_problem_stride = 0;
-  return validate(ctx, &read, B);
+  return validate(ctx, &read, B, allow_wide);
 }
 
 // The two Lbfgs paths: their refusals around the shared ones (T::kRefusesLargeM: the float path words the m limit

@@ -9,6 +9,7 @@
 
 #include "engine_internal.hpp"
 #include "lbfgs_wide_kernel.hpp"
+#include "lbfgs_ask_tell_wide_config.hpp"  // dispatch_wide_eval
 #include "ridge_mfma_kernel.hpp"  // layout constants of the joint-evaluation ridge kernel (not instantiated here)
 
 // ABI layout guards (mirrored by cppnumericalsolvers_amd/capi.py and the C++ host header).
@@ -1067,14 +1068,32 @@ int mi355_lbfgs_fill_x0(mi355_lbfgs_ctx* ctx, int32_t kind, uint64_t seed, int64
 
 int mi355_lbfgs_eval_batch(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const double* x,
                            double* f_out, double* g_out, void* stream_) {
-  int rc = validate(ctx, desc, B);
+  int rc = validate(ctx, desc, B, /*allow_wide=*/true);
   if (rc != MI355_OK) return rc;
   if (desc->objective == MI355_OBJ_SQUARED_ERROR_RIDGE_MFMA)
     return fail(MI355_ERR_UNSUPPORTED, "the matrix-core ridge objective has solve entry points only");
+  const bool wide = desc->n > MI355_LBFGS_MAX_N;
+  if (wide) {
+    // one workgroup per row with the functors of the persistent wide kernel (lbfgs_ask_tell_wide_kernel.hpp, eval_kernel)
+    if (desc->objective != MI355_OBJ_ROSENBROCK && desc->objective != MI355_OBJ_DIAG_QUADRATIC)
+      return fail(MI355_ERR_UNSUPPORTED,
+                  "eval_batch at n > MI355_LBFGS_MAX_N is built for the Rosenbrock and DiagQuadratic objectives (a user "
+                  "objective's workgroup functor has solve entry points only)");
+    if (desc->arithmetic == MI355_ARITH_FMA)
+      return fail(MI355_ERR_UNSUPPORTED, "n > MI355_LBFGS_MAX_N is built in the exact arithmetic");
+    if (desc->lanes_per_problem != 0 || desc->elems_per_lane != 0)
+      return fail(MI355_ERR_INVALID_ARGUMENT, "n > MI355_LBFGS_MAX_N: leave the mapping fields 0");
+  }
   if (B == 0) return MI355_OK;
   if (!x || !f_out) return fail(MI355_ERR_INVALID_ARGUMENT, "null x / f_out");
+  if (wide && !g_out) return fail(MI355_ERR_INVALID_ARGUMENT, "n > MI355_LBFGS_MAX_N: null g_out (the gradient is always written)");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   MI355_ENTER_DEVICE(ctx);
+  if (wide) {
+    rc = upload_params(ctx, desc, 0, 0, stream);
+    if (rc != MI355_OK) return rc;
+    return dispatch_wide_eval(ctx, desc->objective, x, f_out, g_out, ctx->params_dev, B, desc->n, stream);
+  }
   if (desc->objective == MI355_OBJ_SQUARED_ERROR_RIDGE_GRAM) {
     SolveArgs gargs;
     std::memset(&gargs, 0, sizeof(gargs));

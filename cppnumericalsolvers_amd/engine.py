@@ -544,7 +544,10 @@ class LbfgsAskTell:
     .x: the [B, n] float64 tensor VIEW of the evaluation buffer (no copy; valid until close()); rows of finished
     problems hold their returned x, and what is handed back for them is never read.  A solver built with
     dtype=torch.float32 runs the native float path (mi355_lbfgs_ask_tell_f32_*): x0, .x, f, g and the results are
-    float32 then, and a tensor of the other dtype is a ValueError in both directions.  A solver configured with what the
+    float32 then, and a tensor of the other dtype is a ValueError in both directions.  Above n = 256 a float64 solver
+    runs the workgroup-per-problem handle (mi355_lbfgs_ask_tell_wide_*: same protocol, same results as `minimize` at that
+    n bit for bit when fn is `solver.evaluate`; B ((3 + 2 m) n + n) 8 bytes of device memory; the library's mapping only);
+    a float32 solver is refused there.  A solver configured with what the
     path does not build (Hager-Zhang, arithmetic="fma", y history in registers, condition_hessian) raises the
     library's message (EngineError).  Everything runs on the current stream of the solver's device."""
 
@@ -553,8 +556,12 @@ class LbfgsAskTell:
     _prefix_f32 = "mi355_lbfgs_ask_tell_f32_"   # the handle type of a float32 solver
     _listed_suffix = "lbfgs"                    # mi355_ask_tell_compact_lbfgs[_f32], mi355_ask_tell_ids_lbfgs[_f32]
 
+    _prefix_wide = "mi355_lbfgs_ask_tell_wide_"   # ... of a float64 BatchedLbfgs above n = 256 (a workgroup per problem)
+    _wide = False
+
     def _call(self, name, *args):
-        capi.check(getattr(self._lib, (self._prefix_f32 if self._f32 else self._prefix) + name)(*args))
+        prefix = self._prefix_f32 if self._f32 else (self._prefix_wide if self._wide else self._prefix)
+        capi.check(getattr(self._lib, prefix + name)(*args))
 
     def _check_solver(self, solver):
         if type(solver) is not BatchedLbfgs:
@@ -578,6 +585,8 @@ class LbfgsAskTell:
         x0 = x0.contiguous()
         self.solver = solver
         self.B, self.n = (int(v) for v in x0.shape)
+        # above n = 256 a float64 BatchedLbfgs runs the workgroup-per-problem handle; float32 keeps its refusal
+        self._wide = type(solver) is BatchedLbfgs and not self._f32 and self.n > capi.MAX_N
         self._lib = solver.ctx._lib
         d = solver._desc(Objective(capi.OBJ_ROSENBROCK, np.zeros(0), "caller"), self.n)
         d.hessian_condition_stop = solver.condition_hessian
@@ -610,6 +619,8 @@ class LbfgsAskTell:
 
     def _call_listed(self, name, *args):
         """mi355_ask_tell_<name>_<handle type>: the calls of the listed mode"""
+        if self._wide:   # (named after its handle type: mi355_lbfgs_ask_tell_wide_compact / _ids)
+            return self._call(name, *args)
         suffix = self._listed_suffix + ("_f32" if self._f32 else "")
         capi.check(getattr(self._lib, "mi355_ask_tell_%s_%s" % (name, suffix))(*args))
 

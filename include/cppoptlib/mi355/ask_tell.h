@@ -5,6 +5,10 @@
 //   LbfgsAskTell        RAII handle of one batched solve: Ask() is the device pointer of the points to evaluate
 //                       ([B][n], the same pointer for the handle's lifetime), Tell(f_dev, g_dev) hands the values and
 //                       gradients back and returns the number of problems still active, Results(...) copies the states.
+//                       The dimension picks the C handle: mi355_lbfgs_ask_tell_* up to n = 256, above it
+//                       mi355_lbfgs_ask_tell_wide_* (a workgroup per problem; the library's mapping only;
+//                       B ((3 + 2 m) n + n) 8 bytes of device memory).  MinimizeBatchWith and
+//                       MinimizeBatchWithCompaction follow, being loops over the handle.
 //   LbfgsAskTellF32     the same in native float (mi355_lbfgs_ask_tell_f32_*): float x0, points, values, gradients and
 //                       results — a float objective is evaluated in its own precision, never widened
 //   LbfgsbAskTell       the same for Lbfgsb<F, m, MoreThuente>: no box, one shared box, or one box per problem
@@ -21,6 +25,7 @@
 
 #include <cstdint>
 #include <memory>
+#include <new>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -53,17 +58,58 @@ namespace detail {
 
 // What tells the three C handle types apart: the scalar, the handle, its C functions, and the names a failure reports
 // (the class for a null context, "<kPrefix><function>" for a C call).
+// What LbfgsAskTell holds: the C handle its dimension selects — mi355_lbfgs_ask_tell up to n = MI355_LBFGS_MAX_N (a
+// wavefront segment per problem), mi355_lbfgs_ask_tell_wide above (a workgroup per problem).  Exactly one is set.
+struct LbfgsAskTellByDimension {
+  mi355_lbfgs_ask_tell* narrow = nullptr;
+  mi355_lbfgs_ask_tell_wide* wide = nullptr;
+};
 struct LbfgsAskTellApi {
   using Scalar = double;
-  using Handle = mi355_lbfgs_ask_tell;
-  static constexpr auto create = &mi355_lbfgs_ask_tell_create;
-  static constexpr auto x = &mi355_lbfgs_ask_tell_x;
-  static constexpr auto step = &mi355_lbfgs_ask_tell_step;
-  static constexpr auto active = &mi355_lbfgs_ask_tell_active;
-  static constexpr auto results = &mi355_lbfgs_ask_tell_results;
-  static constexpr auto destroy = &mi355_lbfgs_ask_tell_destroy;
-  static constexpr auto compact = &mi355_ask_tell_compact_lbfgs;
-  static constexpr auto ids = &mi355_ask_tell_ids_lbfgs;
+  using Handle = LbfgsAskTellByDimension;
+  static int create(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const double* x0, void* stream,
+                    Handle** out) {
+    *out = nullptr;
+    Handle* h = new (std::nothrow) Handle;
+    if (h == nullptr) Fail("LbfgsAskTell: out of memory");
+    const int rc = (desc != nullptr && desc->n > MI355_LBFGS_MAX_N)
+                       ? mi355_lbfgs_ask_tell_wide_create(ctx, desc, B, x0, stream, &h->wide)
+                       : mi355_lbfgs_ask_tell_create(ctx, desc, B, x0, stream, &h->narrow);
+    if (rc != MI355_OK) {
+      delete h;
+      return rc;
+    }
+    *out = h;
+    return rc;
+  }
+  static int x(Handle* h, const double** x_eval) {
+    return h->wide ? mi355_lbfgs_ask_tell_wide_x(h->wide, x_eval) : mi355_lbfgs_ask_tell_x(h->narrow, x_eval);
+  }
+  static int step(Handle* h, const double* f, const double* g, int64_t* active_host, void* stream) {
+    return h->wide ? mi355_lbfgs_ask_tell_wide_step(h->wide, f, g, active_host, stream)
+                   : mi355_lbfgs_ask_tell_step(h->narrow, f, g, active_host, stream);
+  }
+  static int active(Handle* h, const int64_t** active_dev) {
+    return h->wide ? mi355_lbfgs_ask_tell_wide_active(h->wide, active_dev) : mi355_lbfgs_ask_tell_active(h->narrow, active_dev);
+  }
+  static int results(Handle* h, double* x_out, double* f_out, double* g_out, mi355_lbfgs_progress* progress_out,
+                     void* stream) {
+    return h->wide ? mi355_lbfgs_ask_tell_wide_results(h->wide, x_out, f_out, g_out, progress_out, stream)
+                   : mi355_lbfgs_ask_tell_results(h->narrow, x_out, f_out, g_out, progress_out, stream);
+  }
+  static int destroy(Handle* h) {
+    if (h == nullptr) return MI355_OK;
+    const int rc = h->wide ? mi355_lbfgs_ask_tell_wide_destroy(h->wide) : mi355_lbfgs_ask_tell_destroy(h->narrow);
+    delete h;
+    return rc;
+  }
+  static int compact(Handle* h, int64_t* listed_host, void* stream) {
+    return h->wide ? mi355_lbfgs_ask_tell_wide_compact(h->wide, listed_host, stream)
+                   : mi355_ask_tell_compact_lbfgs(h->narrow, listed_host, stream);
+  }
+  static int ids(Handle* h, const int64_t** ids_dev, int64_t* listed) {
+    return h->wide ? mi355_lbfgs_ask_tell_wide_ids(h->wide, ids_dev, listed) : mi355_ask_tell_ids_lbfgs(h->narrow, ids_dev, listed);
+  }
   static constexpr const char* kClass = "LbfgsAskTell";
   static constexpr const char* kPrefix = "mi355_lbfgs_ask_tell_";
 };

@@ -701,6 +701,34 @@ int mi355_lbfgs_ask_tell_results(mi355_lbfgs_ask_tell* handle, double* x_out, do
                                  mi355_lbfgs_progress* progress_out, void* stream);
 int mi355_lbfgs_ask_tell_destroy(mi355_lbfgs_ask_tell* handle);
 
+/* ---- ask/tell L-BFGS above n = 256: one workgroup per problem (additive, the ABI number stays) ------------------------
+ * The protocol of mi355_lbfgs_ask_tell_* for 256 < n <= MI355_LBFGS_WIDE_MAX_N, as a handle type of its own.  A problem
+ * is owned by a workgroup of 256 threads (1024 for n >= 32768), thread t holds the coordinates t, t + T, ... and every
+ * sum runs in the order of the persistent kernel for this regime, so a callback that evaluates with
+ * mi355_lbfgs_eval_batch (built above n = 256 for Rosenbrock and DiagQuadratic) reproduces mi355_lbfgs_minimize_batch at
+ * that n bit for bit (x, f, g and every field of the progress record).  A step call streams a problem's state through
+ * once per part it runs: the evaluated gradient's pass, the update, the two-loop recursion, the next trial point.
+ * Of desc: n, m (<= 32) and stop are read; objective and the parameter fields are ignored.  MI355_ERR_UNSUPPORTED with a
+ * message that starts "Lbfgs ask/tell wide", before anything is allocated or launched, for: n <= 256 (that is
+ * mi355_lbfgs_ask_tell_create's), Hager-Zhang, MI355_ARITH_FMA, MI355_HISTORY_Y_IN_REGISTERS, hessian_from_functor,
+ * hessian_diagonal, hessian_condition_stop > 0, a trace, per_problem_data, non-zero lanes_per_problem / elems_per_lane.
+ * Device memory of a handle: B ((3 + 2 m) np + n) 8 bytes (np = n rounded up to even: x, g, d, the S and Y rings, and the
+ * evaluation buffer) plus 552 bytes of scalars per problem; an allocation that fails reports the byte count.  The
+ * functions mean what their mi355_lbfgs_ask_tell_* namesakes mean; _compact and _ids are the listed mode of this handle
+ * type, what mi355_ask_tell_compact_lbfgs and mi355_ask_tell_ids_lbfgs (below) are for mi355_lbfgs_ask_tell. */
+typedef struct mi355_lbfgs_ask_tell_wide mi355_lbfgs_ask_tell_wide;
+int mi355_lbfgs_ask_tell_wide_create(mi355_lbfgs_ctx* ctx, const mi355_lbfgs_desc* desc, int64_t B, const double* x0,
+                                     void* stream, mi355_lbfgs_ask_tell_wide** out);
+int mi355_lbfgs_ask_tell_wide_x(mi355_lbfgs_ask_tell_wide* handle, const double** x_eval);
+int mi355_lbfgs_ask_tell_wide_step(mi355_lbfgs_ask_tell_wide* handle, const double* f, const double* g,
+                                   int64_t* active_host, void* stream);
+int mi355_lbfgs_ask_tell_wide_active(mi355_lbfgs_ask_tell_wide* handle, const int64_t** active_dev);
+int mi355_lbfgs_ask_tell_wide_results(mi355_lbfgs_ask_tell_wide* handle, double* x_out, double* f_out, double* g_out,
+                                      mi355_lbfgs_progress* progress_out, void* stream);
+int mi355_lbfgs_ask_tell_wide_destroy(mi355_lbfgs_ask_tell_wide* handle);
+int mi355_lbfgs_ask_tell_wide_compact(mi355_lbfgs_ask_tell_wide* handle, int64_t* listed_host, void* stream);
+int mi355_lbfgs_ask_tell_wide_ids(mi355_lbfgs_ask_tell_wide* handle, const int64_t** ids_dev, int64_t* listed);
+
 /* ---- ask/tell L-BFGS in native float: float objectives the CALLER evaluates -----------------------------------------
  * Lbfgs<F, m, MoreThuente>::Minimize with ScalarType = float in the protocol of mi355_lbfgs_ask_tell_*: a handle type of
  * its own, float arrays where the fp64 functions take double arrays, the same meaning of every call.  The arithmetic is
@@ -776,7 +804,8 @@ int mi355_lbfgsb_ask_tell_asks(mi355_lbfgsb_ask_tell* handle, int64_t counts_hos
  * (2 B int64, B n scalars, B / 64 + 1 int64; freed by _destroy); if that fails it returns MI355_ERR_HIP and the handle
  * goes on unlisted.  A handle that is never compacted allocates and launches exactly what it did before.
  * _ids: the DEVICE list (valid until the next _compact or _destroy) and its length; before the first _compact: NULL and
- * B.  One function per handle type: ..._lbfgs for mi355_lbfgs_ask_tell, ..._lbfgs_f32 and ..._lbfgsb for the others. */
+ * B.  One function per handle type: ..._lbfgs for mi355_lbfgs_ask_tell, ..._lbfgs_f32 and ..._lbfgsb for the others
+ * (mi355_lbfgs_ask_tell_wide has mi355_lbfgs_ask_tell_wide_compact and mi355_lbfgs_ask_tell_wide_ids, above). */
 int mi355_ask_tell_compact_lbfgs(mi355_lbfgs_ask_tell* handle, int64_t* listed_host, void* stream);
 int mi355_ask_tell_compact_lbfgs_f32(mi355_lbfgs_ask_tell_f32* handle, int64_t* listed_host, void* stream);
 int mi355_ask_tell_compact_lbfgsb(mi355_lbfgsb_ask_tell* handle, int64_t* listed_host, void* stream);
