@@ -169,6 +169,36 @@ def diag_quadratic_k(n):
     return log2_ceil(n) + 4, 1, 1
 
 
+# ---- dense quartic (the example functor, objective 101) ------------------------------------------------------------------
+#   f(x) = x . (S x) / 2 - b . x + (kappa / 4) sum_i x_i^4,   g = S x - b + kappa x^3,   H = S + 3 kappa diag(x^2)
+# S is used as given (never symmetrised): H_ij = S_ij.
+def _dense_quartic(ar, x, S, b, kappa, hessian=False):
+    n = len(x)
+    sx = [mp.fdot(S[i], x) for i in range(n)]
+    f = ar.sub(mp.fdot(x, sx) / 2, mp.fdot(b, x)) + kappa / 4 * sum(v ** 4 for v in x)
+    g = [ar.sub(sx[j], b[j]) + kappa * x[j] ** 3 for j in range(n)]
+    H = None
+    if hessian:
+        H = [[S[i][j] + (3 * kappa * x[i] * x[i] if i == j else 0) for j in range(n)] for i in range(n)]
+    return f, g, H
+
+
+def dense_quartic(x, S, b, kappa, hessian=False):
+    """S: [n, n] with S[i][j] = S(i, j) (a numpy array or rows of floats)"""
+    return _both(_dense_quartic, vec(x), [vec(r) for r in S], vec(b), mpf(float(kappa)), hessian=hessian)
+
+
+def dense_quartic_k(n):
+    """(k_f, k_g, k_H), examples/user_objective_dense/dense_quartic.hpp.
+    f: (S x)_i is an ascending chain of n (first term a product), x_i (S x)_i one more, the sum over the coordinates
+       ceil(log2 n) levels (a lane's coordinates as an ascending chain: at four per lane three links for two levels, one
+       deeper), the halving exact, - b.x and + the quartic part two more: n + ceil(log2 n) + 4.  (b.x and the quartic part,
+       x x, q q, the sum, (kappa / 4) . are shorter and join at the last two links.)
+    g: the chain of n, - b_i, + kappa (q x): n + 2 (q, q x, kappa . is a chain of 3 that joins at the last link).
+    H: 3 kappa, x x, their product, S_ii + .: 4 on the diagonal; off it a copy, exact."""
+    return n + log2_ceil(n) + 4, n + 2, 4
+
+
 # ---- ridge least squares -------------------------------------------------------------------------------------------------
 #   f(x) = ||A x - y||^2 + lam ||x||^2,   g = 2 A^T r + 2 lam x,   r = A x - y
 # ONE definition for the four device forms (the VALU form, the matrix-core form, the two normal-equation forms).  The

@@ -18,6 +18,9 @@ The rules of the reference's `Lbfgs::OptimizationStep` (solver/lbfgs.h), restate
            recursion, oldest to newest, rho = 1 / s^T y; H_0 = gamma I, in Second mode diag(1 / (|H_jj| + eps)) (:133-134).
            For n > DENSE_MAX the same matrix is applied through its compact representation (Byrd, Nocedal, Schnabel 1994,
            eq. 3.1: an identity of the product form, m x m systems only); tests/test_step_lib.py holds the two to 1e-40.
+`GradientDescent` (solver/gradient_descent.h:64-73; Rules(solver="gradient_descent")): the same audit with H = I and no
+pairs — s a positive multiple of -g_k within the bound with K = 0, the line-search conditions on the solve's own numbers; a
+refused search (g.g underflows to 0) steps to x - g.
 Dense `Bfgs` (solver/bfgs.h): the same update from H_0 = I over every pair with y^T s > eps ||s|| ||y|| (:125); H back to I
 and steepest descent when g^T (-H g) > 0 or NaN (:88-92).
 
@@ -297,7 +300,18 @@ def audit_problem(xs, gs, fs, rules, hess_diag=None, what=""):
             continue
         if alive:
             reset = False
-            if rules.solver == "bfgs":
+            steepest = rules.solver == "gradient_descent"      # H = I and no pairs: the direction is g itself
+            if steepest:
+                # gradient_descent.h:64-73 searches along -g from x_k.  The refused search is a rule: where g.g underflows to
+                # 0 the search returns its initial step 1 and the iterate is x - g, evaluated again (more_thuente.h:152-156)
+                if all(float(e) * float(e) == 0.0 for e in g):
+                    if not np.array_equal(np.asarray(xs[k + 1], dtype=work),
+                                          np.asarray(xs[k], dtype=work) - np.asarray(gs[k], dtype=work)):
+                        rep.bad.append("%s iteration %d: a refused search did not step to x - g" % (what, k + 1))
+                    rep.audited += 1
+                    through = k + 1
+                    continue
+            elif rules.solver == "bfgs":
                 if H is None:
                     H = [[mpf(1) if i == j else mpf(0) for j in range(n)] for i in range(n)]
                     Habs = [row[:] for row in H]
@@ -351,6 +365,7 @@ def audit_problem(xs, gs, fs, rules, hess_diag=None, what=""):
             if alive:
                 if reset:
                     rep.resets += 1
+                if reset or steepest:
                     d, M0, M1, K = g, absv(g), absv(g), 0
                 dd = fdot(d, d)
                 alpha = -fdot(s, d) / dd if dd > 0 else mpf(0)
@@ -376,7 +391,7 @@ def audit_problem(xs, gs, fs, rules, hess_diag=None, what=""):
         if not alive:
             rep.unaudited += 1
         _line_search(rules, rep, "%s iteration %d" % (what, k + 1), F[k], F[k + 1], g, G[k + 1], s, X[k], X[k + 1], D)
-        if not alive:
+        if not alive or rules.solver == "gradient_descent":      # (gradient descent keeps no state)
             continue
         # ---- the state after the step -------------------------------------------------------------------------------------
         sy, say = fdot(s, y), fdot(absv(s), absv(y))

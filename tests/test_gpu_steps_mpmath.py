@@ -229,15 +229,19 @@ def test_lbfgsb_keeps_the_box_and_the_decrease(ctx, name, start, n, m, per_probl
 
 @pytest.mark.parametrize("n,m", Sc.DENSE_QUARTIC_SHAPES)
 def test_dense_quartic_functor_steps(n, m):
-    """the dense quartic example functor (objective 101 of the library built with it): direction and line search, the two
-    checks that need no definition of the objective"""
+    """the dense quartic example functor (objective 101 of the library built with it): direction and line search, and the
+    traced value and gradient of every iterate against hp_lib.dense_quartic"""
     import cppnumericalsolvers_amd as amd
+    import hp_lib
     params, x0 = Sc.dense_quartic(n)
+    S, b, kappa = params[:n * n].reshape(n, n).T, params[n * n:n * n + n], params[-1]
+    evaluate = lambda x: hp_lib.dense_quartic(x, S, b, kappa)
     user = amd.Context(0, library=os.path.join(REPO, "cppnumericalsolvers_amd", "libmi355_lbfgs_tr.so"))
     try:
         make = lambda stop: amd.BatchedLbfgs(m=m, stopping_progress=stop, context=user, arithmetic="exact")
         trajectories = _traced(make, amd.Objective(101, params, "dense_quartic"), x0, m)
     finally:
         user.close()
-    rep = St.audit_case(trajectories, Sc.rules_of("exact", m), what="dense quartic n=%d m=%d" % (n, m))
+    rep = St.audit_case(trajectories, Sc.rules_of("exact", m), evaluate, hp_lib.dense_quartic_k(n)[:2],
+                        what="dense quartic n=%d m=%d" % (n, m))
     _finish("dense quartic n=%d" % n, [(m, "dense quartic n=%d m=%d" % (n, m), rep)])
